@@ -7,7 +7,21 @@ update over one synthetic 224x224 batch of 256 images per GPU (data/imagenet.py:
 seeded U(-1,1) data, random labels), bf16 activations/weights with fp32 master weights,
 gradients and BN statistics. Inputs are resident in HBM before the timed region.
 
-Rank 0 prints ONE JSON line (contract in the task statement), including
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, the output dump
+when `--dump-outputs DIR` is given, and the result line (metric, value, unit, higher_is_better, dtype,
+ms_per_step and the run's configuration). `--dump-outputs DIR` writes what the last timed step computed --
+the softmax output, the updated fp32 parameters, the gradients and the BatchNorm moving statistics, as a
+caller of Module.get_outputs() / get_params() reads them -- to DIR/<name>.npy (float32; parameters and
+gradients as a fixed seeded sample, well under 64 MB in all). Inputs and initial weights are seeded. The default
+kernels sum BatchNorm reductions and weight gradients with atomics, in an order that changes from run to run; that
+rounding flips bf16 roundings downstream, and this workload (noise images, random labels) amplifies them: one
+step's gradients differ by ~1.5 % between two runs, after a few updates by ~100 %. So a run with --dump-outputs
+switches the library to its deterministic mode (RN_DETERMINISTIC=1: fixed summation orders, measured ~4 % slower
+per step, reported as "deterministic": true), in which two runs with the same arguments write bit-identical arrays
+and two builds can be compared array for array. RN_DETERMINISTIC=0 in the environment keeps the default kernels.
+
+`--full` adds every other measurement (each takes steps of its own, all outside the timed region except the
+event records on the last timed step). With it rank 0's JSON line also holds
   roofline     : the dominant kernel family (most kernel time per step in a serialised calibration
                  step; every family's time is listed) -- algorithmic FLOP and bytes per launch /
                  average launch duration from HIP events around every launch of that family on the
@@ -302,6 +316,33 @@ def c1_module_cpu(batch=128, steps=10):
                       "%d timed steps (%.1f s)" % (batch, steps, dt)}
 
 
+DUMP_SAMPLE = 1 << 22  # elements kept of the parameters and of the gradients (16 MB of float32 each)
+
+
+def dump_outputs(dirname, mod):
+    """What the last step left for a caller of the Module: the softmax output (get_outputs), the updated fp32
+    parameters and the BatchNorm moving statistics (this rank's, as get_params reads them), and the step's
+    gradients, in the reference's layouts and in the plan's parameter order. Parameters and gradients are
+    concatenated and, when longer than DUMP_SAMPLE, reduced to the same fixed seeded sample of positions
+    (sorted, so neighbours stay neighbours)."""
+    import numpy as np
+    ex = mod.executor
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"prob": mod.get_outputs()[0].asnumpy()}
+    names = list(ex.plan.param_names)
+    arrays["params"] = np.concatenate([ex.get_param(n).reshape(-1) for n in names])
+    arrays["grads"] = np.concatenate([ex.get_param(n, grad=True).reshape(-1) for n in names])
+    if ex.plan.aux_names:
+        arrays["aux"] = np.concatenate([ex.get_aux(n).reshape(-1) for n in ex.plan.aux_names])
+    total = arrays["params"].size
+    if total > DUMP_SAMPLE:
+        pick = np.sort(np.random.default_rng(20240607).choice(total, DUMP_SAMPLE, replace=False))
+        arrays["params"] = arrays["params"][pick]
+        arrays["grads"] = arrays["grads"][pick]
+    for name, v in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -399,6 +440,14 @@ def main():
                     help="BASELINE.json configs: resnet50 = C2/C3 (the headline), resnext50 = C4 "
                          "(32x4d, grouped convs), resnet50_int8 = C5 (symbol/resnet_int8.py QAT graph)")
     ap.add_argument("--bucket-mb", type=float, default=25.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-family roofline records (a serialised "
+                         "calibration step, HIP events on the last timed step), the PCIe-inclusive leg and the CPU "
+                         "baselines (--no-cpu-baseline, --cpu-*, --pcie-steps apply to these legs)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (softmax output, updated parameters, gradients, "
+                         "BatchNorm moving statistics) as DIR/<name>.npy; runs the library's deterministic mode "
+                         "(RN_DETERMINISTIC=1 unless the environment sets it) so that the arrays repeat from run to run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=32)
     ap.add_argument("--cpu-steps", type=int, default=2)
@@ -411,6 +460,9 @@ def main():
                     help="replay the captured step as one HIP graph (auto: on for a single GPU)")
     a = ap.parse_args()
 
+    if a.dump_outputs:
+        # before the library is loaded and the plan is made: both read it (rn/lib.py, rn/executor.py)
+        os.environ.setdefault("RN_DETERMINISTIC", "1")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and (a.gpus or 1) > 1:
         sys.exit(launch_ranks(a.gpus, sys.argv[1:]))
@@ -464,8 +516,10 @@ def main():
     mod.forward(batch, is_train=True)  # H2D once: inputs resident from here on
     torch.cuda.synchronize()
 
-    pinned = mx.io.DataBatch(data=[mx.nd.array(data, ctx=mx.Context("cpu_pinned", 0))],
-                             label=[mx.nd.array(label, ctx=mx.Context("cpu_pinned", 0))])
+    pinned = None
+    if a.full or a.host_input:
+        pinned = mx.io.DataBatch(data=[mx.nd.array(data, ctx=mx.Context("cpu_pinned", 0))],
+                                 label=[mx.nd.array(label, ctx=mx.Context("cpu_pinned", 0))])
 
     # (the data-gradient chain on a high-priority stream -- RN_MAIN_PRIORITY, rounds 3-5 -- measured slower since the
     # weight gradients' grids were sized for part of the chip, profiles/r04/priority: removed in round 6)
@@ -477,21 +531,24 @@ def main():
     for _ in range(max(a.warmup, 1)):
         step()
     torch.cuda.synchronize()
-    fams = calibrate_families(torch, ex, mod)
+    fams = calibrate_families(torch, ex, mod) if a.full else {}
     # roofline.kernel: the family with the most kernel time per step (serialised calibration step), as the
     # contract says -- with the side stream on that is the weight-gradient family. critical_path: the
     # compute (data-gradient) stream's largest family, which sets the step when the weight gradients
     # run overlapped beside it (rn_set_tuning 21 sizes them for part of the chip); both are timed with
     # HIP events on the stream each launch runs on, every family's time is listed
     side = bool(getattr(ex, "_side_idx", None)) and ex.side_enabled
-    dom = max(fams, key=lambda f: fams[f][0])
-    crit_fams = [f for f in fams if not (side and f.startswith("wgrad"))] or list(fams)
-    crit = max(crit_fams, key=lambda f: fams[f][0])
-    wg = next((f for f in fams if f.startswith("wgrad")), None)  # the weight-gradient family (side stream)
-    timers = {dom: FamilyTimer(torch, ex, dom)}
-    for f in (crit, wg):
-        if f is not None and f not in timers:
-            timers[f] = FamilyTimer(torch, ex, f)
+    dom = crit = wg = None
+    timers = {}
+    if a.full:
+        dom = max(fams, key=lambda f: fams[f][0])
+        crit_fams = [f for f in fams if not (side and f.startswith("wgrad"))] or list(fams)
+        crit = max(crit_fams, key=lambda f: fams[f][0])
+        wg = next((f for f in fams if f.startswith("wgrad")), None)  # the weight-gradient family (side stream)
+        timers[dom] = FamilyTimer(torch, ex, dom)
+        for f in (crit, wg):
+            if f is not None and f not in timers:
+                timers[f] = FamilyTimer(torch, ex, f)
     # auto: one HIP graph on a single GPU -- unless the executor runs its weight gradients on a side
     # stream: the graph replay serialises the two branches, eager launches overlap them (measured
     # 22.30 vs 22.93 ms per step for the graph with everything on one stream)
@@ -533,13 +590,15 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(a.steps):
-        if i == a.steps - 1 and not use_graph:
+        if a.full and i == a.steps - 1 and not use_graph:
             instrument()
         run()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, mod)  # before any further step overwrites the last timed step's results
     overlap = None
     if reducer is not None and reducer.timing:
         reducer.timing = False
@@ -549,7 +608,7 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             overlap["exposed_ms_max_over_ranks"] = round(float(t[1].item()), 3)
             overlap["exposed_ms_mean_max_over_ranks"] = round(float(t[0].item()), 3)
-    if use_graph:
+    if use_graph and a.full:
         # graph nodes cannot carry timing events: time the family's launches in one eager step
         # run directly after the timed region (same kernels and shapes as the replayed graph)
         for t in timers.values():
@@ -567,7 +626,7 @@ def main():
     # stream, double-buffered, overlapping the previous step
     pcie = None
     psteps = a.steps // 2 if a.pcie_steps is None else a.pcie_steps
-    if psteps > 0 and not a.host_input:
+    if a.full and psteps > 0 and not a.host_input:
         for _ in range(2):
             step(pinned)
         if world > 1:
@@ -606,26 +665,32 @@ def main():
             "config": {"workload": "%s train step, batch %d/GPU, %dx%d" % (
                 workload, a.batch, a.image, a.image), "model": model_name, "global_batch": a.batch * world,
                 "seq_len": None, "parallelism": "dp%d" % world, "per_gpu_images_per_sec": round(value / world, 2)},
-            "roofline": dict(roof[dom], dominant_rule="most kernel time per step (serialised calibration step)",
-                             concurrent_streams=2 if (ex._side_idx and ex.side_enabled) else 1,
-                             step_tflops=round(flops_step / (ms_step * 1e-3) / 1e12, 2),
-                             step_frac=round(flops_step / (ms_step * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
-                             families_ms_per_step={f: round(v[0], 3) for f, v in fams.items()}),
-            # the compute stream's largest family: the step's critical path while the weight gradients
-            # run overlapped on the side stream (the same record as roofline's; equal to it with one stream)
-            "critical_path": dict(roof[crit], rule="most kernel time per step among the compute stream's "
-                                                   "families" if side else "one stream: the dominant family"),
-            # the weight gradients (the side stream's family: in-step with part of the chip's grids beside the
-            # data-gradient chain, solo = the serialised calibration step on the whole chip)
-            "weight_gradients": roof.get(wg),
             "outputs_finite": finite,
             "hip_graph": bool(use_graph),
-            "family_timing": ("one eager step right after the timed region" if use_graph else
-                              "HIP events on the last of the %d timed steps" % a.steps),
-            "inputs":"pinned host batch copied every step (PCIe-inclusive)" if a.host_input else
+            "inputs": "pinned host batch copied every step (PCIe-inclusive)" if a.host_input else
                       "resident in HBM",
-            "pcie_inclusive": pcie,
+            "full": bool(a.full),
+            "deterministic": os.environ.get("RN_DETERMINISTIC", "0") == "1",
         }
+        if a.dump_outputs:
+            out["dumped_outputs"] = os.path.abspath(a.dump_outputs)
+        if a.full:
+            out["roofline"] = dict(
+                roof[dom], dominant_rule="most kernel time per step (serialised calibration step)",
+                concurrent_streams=2 if (ex._side_idx and ex.side_enabled) else 1,
+                step_tflops=round(flops_step / (ms_step * 1e-3) / 1e12, 2),
+                step_frac=round(flops_step / (ms_step * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
+                families_ms_per_step={f: round(v[0], 3) for f, v in fams.items()})
+            # the compute stream's largest family: the step's critical path while the weight gradients
+            # run overlapped on the side stream (the same record as roofline's; equal to it with one stream)
+            out["critical_path"] = dict(roof[crit], rule="most kernel time per step among the compute stream's "
+                                                         "families" if side else "one stream: the dominant family")
+            # the weight gradients (the side stream's family: in-step with part of the chip's grids beside the
+            # data-gradient chain, solo = the serialised calibration step on the whole chip)
+            out["weight_gradients"] = roof.get(wg)
+            out["family_timing"] = ("one eager step right after the timed region" if use_graph else
+                                    "HIP events on the last of the %d timed steps" % a.steps)
+            out["pcie_inclusive"] = pcie
         if force_ar or world > 1:
             nbytes = int(ex.grad.numel()) * ex.grad.element_size()
             out["allreduce"] = {"backend": dist.get_backend(), "world": world, "buckets": len(ex.buckets()),
@@ -638,7 +703,7 @@ def main():
                 out["allreduce"].update(overlap)
             if force_ar:
                 out["allreduce"]["note"] = "RCCL bucket all-reduce hooks on at N=1 (RN_BENCH_ALLREDUCE=1)"
-        if world == 1 and not a.no_cpu_baseline and a.model == "resnet50":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.model == "resnet50":
             try:
                 out["cpu_baseline"] = cpu_baseline(a.cpu_batch, a.cpu_steps)
                 out["cpu_baseline_c1"] = cpu_baseline_c1()

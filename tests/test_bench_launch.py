@@ -55,8 +55,9 @@ def test_bench_gpus2_runs_two_ranks(gpu):
     """`python bench.py --gpus 2` on the one-GPU box with gloo as the transport: two rank processes
     share cuda:0 and the JSON line reports the two-rank job (whole-job images/s, dp2, global batch
     512, the all-reduce backend and buckets)."""
-    cmd = [sys.executable, "-u", BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-           "--pcie-steps", "0"]
+    # --full: the overlap evidence and the family timing asserted below are not part of a plain run
+    cmd = [sys.executable, "-u", BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
+           "--no-cpu-baseline", "--pcie-steps", "0"]
     r = subprocess.run(cmd, env=_env(RN_DIST_BACKEND="gloo"), capture_output=True, text=True, timeout=600,
                        cwd=REPO)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -147,3 +148,91 @@ def test_pmc_traffic_reads_the_committed_summary(tmp_path):
     for m in ("resnext50", "resnet50_int8"):
         p = bench.pmc_json_path(m)
         assert p is None or p.endswith("pmc_hbm_bytes_per_launch_%s.json" % m), p
+
+
+def _cifar_module_after_one_step():
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench  # noqa: F401  (puts the package on sys.path)
+    import mxnet as mx
+    from rn import graphs
+    mod = mx.mod.Module(graphs.resnet20_cifar(), context=mx.cpu())
+    mod.bind(data_shapes=[("data", (4, 3, 32, 32))], label_shapes=[("softmax_label", (4,))])
+    mx.random.seed(2)
+    mod.init_params(mx.init.Xavier(rnd_type="gaussian", factor_type="in", magnitude=2))
+    mod.init_optimizer(kvstore="local", optimizer="sgd",
+                       optimizer_params={"learning_rate": 0.1, "wd": 1e-4, "momentum": 0.9})
+    rng = np.random.default_rng(0)
+    b = mx.io.DataBatch(data=[mx.nd.array(rng.uniform(-1, 1, (4, 3, 32, 32)).astype(np.float32))],
+                        label=[mx.nd.array(rng.integers(0, 10, 4).astype(np.float32))])
+    mod.forward(b, is_train=True)
+    mod.backward()
+    mod.update()
+    return mod
+
+
+def test_dump_outputs_writes_the_steps_arrays(tmp_path, monkeypatch):
+    """bench.dump_outputs on the host executor (ResNet-20, one step): the softmax output whole, parameters and
+    gradients concatenated in the plan's order and reduced to one fixed sample of positions when longer than
+    DUMP_SAMPLE, the moving statistics; float32 files; the same state gives the same files."""
+    import numpy as np
+    mod = _cifar_module_after_one_step()
+    import bench
+    ex = mod.executor
+    names = list(ex.plan.param_names)
+    params = np.concatenate([ex.get_param(n).reshape(-1) for n in names])
+    grads = np.concatenate([ex.get_param(n, grad=True).reshape(-1) for n in names])
+    bench.dump_outputs(str(tmp_path / "whole"), mod)
+    got = {f[:-4]: np.load(str(tmp_path / "whole" / f)) for f in sorted(os.listdir(str(tmp_path / "whole")))}
+    assert sorted(got) == ["aux", "grads", "params", "prob"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert np.array_equal(got["prob"], mod.get_outputs()[0].asnumpy()) and got["prob"].shape == (4, 10)
+    assert np.array_equal(got["params"], params) and np.array_equal(got["grads"], grads)
+    assert np.abs(got["grads"]).max() > 0
+    assert got["aux"].size == sum(int(np.prod(ex.aux_off[n][1])) for n in ex.plan.aux_names)
+    # a longer parameter vector than the cap: the same sorted sample of positions for parameters and gradients
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), mod)
+    s1 = {n: np.load(str(tmp_path / "s1" / (n + ".npy"))) for n in got}
+    s2 = {n: np.load(str(tmp_path / "s2" / (n + ".npy"))) for n in got}
+    assert all(np.array_equal(s1[n], s2[n]) for n in got)
+    assert s1["params"].shape == s1["grads"].shape == (1000,)
+    pos = np.sort(np.random.default_rng(20240607).choice(params.size, 1000, replace=False))
+    assert np.array_equal(s1["params"], params[pos]) and np.array_equal(s1["grads"], grads[pos])
+    assert np.array_equal(s1["prob"], got["prob"]) and np.array_equal(s1["aux"], got["aux"])
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dump(gpu, tmp_path):
+    """A plain `bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR`: the headline fields and nothing that
+    takes runs of its own (no roofline records, PCIe leg or CPU baselines: those are --full's), --steps timed
+    steps, and the last timed step's arrays as finite float32 .npy files of at most 64 MB in all. A second run
+    with the same arguments writes the same bits (the dump runs the deterministic mode)."""
+    import numpy as np
+    d = tmp_path / "dump"
+    env = {k: v for k, v in _env().items() if k != "RN_DETERMINISTIC"}
+    for out_dir in (tmp_path / "again", d):
+        cmd = [sys.executable, "-u", BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs",
+               str(out_dir)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=REPO)
+        assert r.returncode == 0, r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["full"] is False and out["deterministic"] is True
+    assert out["unit"] == "images/sec" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+    assert out["ms_per_step"] > 0 and abs(out["value"] * out["ms_per_step"] / 1e3 - 256) < 0.5
+    for key in ("roofline", "critical_path", "weight_gradients", "pcie_inclusive", "cpu_baseline", "family_timing"):
+        assert key not in out, key
+    assert out["outputs_finite"]
+    files = sorted(os.listdir(str(d)))
+    assert files == ["aux.npy", "grads.npy", "params.npy", "prob.npy"]
+    arrays = {f: np.load(str(d / f)) for f in files}
+    for f in files:
+        assert np.array_equal(arrays[f], np.load(str(tmp_path / "again" / f))), f
+    assert sum(v.nbytes for v in arrays.values()) <= 64 << 20
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in arrays.values())
+    assert arrays["prob.npy"].shape == (256, 1000)
+    assert np.allclose(arrays["prob.npy"].sum(axis=1), 1.0, atol=1e-3)
+    assert arrays["params.npy"].shape == arrays["grads.npy"].shape and np.abs(arrays["grads.npy"]).max() > 0

@@ -10,7 +10,7 @@ run() {  # $1 = pass name, rest = counters
   timeout -k 10 400 rocprofv3 --pmc "$@" --kernel-trace -d gpurun_out/pmc_${tag}_$name -o run \
     --output-format csv -- python3 bench.py $BENCH_ARGS || exit $?
 }
-BENCH_ARGS="$*"
+BENCH_ARGS="--full $*"  # the same launches per pass as the committed summaries (calibration step included)
 run fetch FETCH_SIZE
 run write WRITE_SIZE
 run sq SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE \
