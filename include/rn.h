@@ -51,7 +51,8 @@ typedef struct rn_conv_desc {
   int32_t p, q;                   /* output spatial size, filled by rn_conv_desc_init         */
   int32_t grouped_direct;         /* filled by rn_conv_desc_init: 1 = this grouped 3x3 runs the
                                      direct v_dot2 kernels with compact weight copies (see
-                                     rn_conv_pack_numel); fixed for the descriptor's lifetime    */
+                                     rn_conv_pack_numel), 2 = the depthwise kernels (one channel
+                                     per group); fixed for the descriptor's lifetime             */
 } rn_conv_desc;
 
 /* Validate and fill p, q (MXNet 'valid' convention: p = (h + 2*pad - r)/stride + 1). */
@@ -200,7 +201,13 @@ int64_t rn_conv_pack_numel(const rn_conv_desc* d, int32_t which);
  * rn_conv_desc_init sets from rn_set_tuning 15 at that time): that
  * mode's copy is compact, [c/8][tap][8][G] with G = c/groups -- w_krsc[k/8][tap][k%8][c'] =
  * w[k][tap][c'], w_crsk[c/8][tap][c%8][k'] = w[g*G + k'][8 - tap][c - g*G], g = c/G -- and
- * rn_conv_fwd / rn_conv_bwd_data multiply it with v_dot2_f32_bf16 (no bias, statistics or BN fusions). */
+ * rn_conv_fwd / rn_conv_bwd_data multiply it with v_dot2_f32_bf16 (no bias, statistics or BN fusions).
+ * Depthwise (d->grouped_direct = 2: bf16, 3x3 pad 1, groups = c = k <= 1024, c % 8 == 0, stride 1 or 2;
+ * set by rn_conv_desc_init unless rn_set_tuning 28 = 1 at that time): both copies are [tap][c], 9 c
+ * elements -- w_krsc[tap][c] = w[c][tap], w_crsk[tap][c] = w[c][8 - tap] -- read by dwconv_fwd_kernel /
+ * dwconv_dgrad_kernel (no bias, statistics or BN fusions; rn_conv_tile is 0); the weight gradient
+ * (dwconv_wgrad_kernel; not the stride-2 14 x 14 x 512 shape, which keeps the block-diagonal tile) always
+ * needs the slab workspace of rn_conv_wgrad_ws_bytes. */
 int rn_conv_weight_pack(const rn_conv_desc* d, const float* w_master, void* w_krsc, void* w_crsk,
                         rn_stream_t stream);
 /* rn_conv_weight_pack for count layers (host arrays: descs[i], w_masters[i], w_krsc[i], w_crsk[i],
@@ -668,7 +675,10 @@ const char* rn_last_error(void);
  *      only on the tile,
  * 22 = 1: the BatchNorm-folded int8 quantizers (rn_quant_int8_fwd_codes_bn[2]) form every quotient
  *      v / unit by division (default 0: v * (1 / unit), the division only where that product lies
- *      within 2^-21 |v / unit| of a half-integer -- the same codes bit for bit, fewer instructions). */
+ *      within 2^-21 |v / unit| of a half-integer -- the same codes bit for bit, fewer instructions),
+ * 28 = 1 at rn_conv_desc_init time: depthwise 3x3 convolutions (groups = c = k) on the block-diagonal
+ *      tiles (default 0: the depthwise kernels, d->grouped_direct = 2); 28 = n >= 2: those kernels on at
+ *      most n workgroups (rounded up to a whole number of chunk periods; tests of the work-item loop). */
 int rn_set_tuning(int32_t key, int32_t value);
 int32_t rn_version(void);
 /* Build id baked in at compile time: a hash of the sources (csrc/*.hip, csrc/*.h, include/rn.h) and the

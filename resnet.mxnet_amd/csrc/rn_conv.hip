@@ -2965,8 +2965,8 @@ __global__ void pack_group_direct_kernel(const float* __restrict__ wm, bf16_t* _
 }
 
 // Many grouped compute copies in one launch (rn_conv_weight_pack_multi): blockIdx.y = copy, the
-// items travel by value in the kernel argument. Element maps as pack_group_direct_kernel (direct)
-// and pack_group_kernel (block-diagonal).
+// items travel by value in the kernel argument. Element maps as pack_group_direct_kernel (direct = 1),
+// pack_dw_kernel (direct = 2, depthwise) and pack_group_kernel (block-diagonal).
 struct GpackItem {
   const float* wm;
   void* out;
@@ -2985,7 +2985,10 @@ __global__ __launch_bounds__(256) void pack_group_multi_kernel(const GpackBatch 
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < p.total;
        i += (int64_t)gridDim.x * blockDim.x) {
     float v = 0.f;
-    if (p.direct) {  // [C/8][9][8][G]
+    if (p.direct == 2) {  // depthwise [9][C], as pack_dw_kernel
+      const int t = (int)(i / p.ncols), c = (int)(i - (int64_t)t * p.ncols);
+      v = wm[c * 9 + (p.transpose ? 8 - t : t)];
+    } else if (p.direct) {  // [C/8][9][8][G]
       const int G = p.cpg;
       const int u = (int)(i % G), t = (int)(i / G);
       const int o = t % 8, t2 = t / 8;
@@ -4051,6 +4054,315 @@ int gd_launch(const rn_conv_desc* d, int mode, const void* x, const void* w, voi
   return rn_check_launch(mode == 0 ? "grouped_direct_fwd" : "grouped_direct_dgrad");
 }
 
+// ---- depthwise 3x3 convolution (one channel per group: MobileNet's conv_N_dw, symbol/mobilenet.py:38-52).
+// 18 FLOP per 4 bytes moved: streaming kernels, bounded by HBM bytes; the block-diagonal MFMA tiles would
+// multiply 63 packed zeros for every product. bf16, NHWC, groups == c == k, pad 1, stride 1 or 2, any
+// c % 8 == 0 up to 1024. Lane = (pixel column, 8-channel chunk), chunks fastest: the lanes of a wave
+// instruction read consecutive 16-byte chunks of whole pixel rows. A work item is one column of a run of PR
+// consecutive output rows: every input row of the run is loaded once (its three tap columns, unpacked to
+// fp32 once) and multiplied into the up to three output rows it belongs to, whose sums stay in registers
+// until their last tap row arrived -- per output row 1 + 2 / PR row loads instead of 3. The grid is sized
+// from the CU count and rounded so that its thread count is a multiple of the chunk count: a lane keeps
+// its chunk over the whole work-item loop, and the chunk's weights ([tap][c], the compact copy) stay in 72
+// fp32 registers for the kernel's lifetime. fp32 sums in the fixed order tap row 0, 1, 2 (columns 0, 1, 2
+// within a row), rounded to bf16 once; rows and columns outside the image are never loaded and add nothing.
+struct DwArgs {
+  const bf16_t* x;    // the gathered tensor [N][H][W][C] (forward: x; data gradient: dy; weight gradient: x)
+  const bf16_t* w;    // compact copy [tap][C] (data gradient: taps mirrored)
+  bf16_t* y;          // the output [N][P][Q][C]
+  const bf16_t* add;  // nullable, added to the output
+  const bf16_t* dy;   // weight gradient: [N][P][Q][C]
+  float* slab;        // weight gradient: [workgroup][C][9] partial sums
+  int H, W, P, Q, C, nchunk, pb;  // pb = row runs per image
+  uint32_t items;                 // N * pb * Q * nchunk
+  FastDiv fdC, fdQ, fdPB;
+};
+__device__ __forceinline__ void dw_load_w(const DwArgs& a, int chunk, float (&wf)[9][8]) {
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+    chunk_to_f(*reinterpret_cast<const uint4*>(a.w + (int64_t)t * a.C + chunk * 8), wf[t], (const bf16_t*)nullptr);
+}
+// item -> image n, row run pr, column q (the chunk is the lane's own)
+__device__ __forceinline__ void dw_item(const DwArgs& a, uint32_t it, uint32_t& n, int& pr, int& q) {
+  const uint32_t t = fdiv(it, a.fdC);
+  const uint32_t t2 = fdiv(t, a.fdQ);
+  q = (int)(t - t2 * a.Q);
+  n = fdiv(t2, a.fdPB);
+  pr = (int)(t2 - n * a.pb);
+}
+// three consecutive pixels' chunks from column w0 of one row, zero outside [0, W)
+__device__ __forceinline__ void dw_load3(const bf16_t* row, int w0, int W, int64_t cs, float (&xf)[3][8]) {
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    const int w = w0 + s;
+    const uint4 v = (w >= 0 && w < W) ? *reinterpret_cast<const uint4*>(row + (int64_t)w * cs) : make_uint4(0, 0, 0, 0);
+    chunk_to_f(v, xf[s], (const bf16_t*)nullptr);
+  }
+}
+__device__ __forceinline__ void dw_store(const DwArgs& a, int64_t off, float (&acc)[8]) {
+  if (a.add) {
+    float f[8];
+    chunk_to_f(*reinterpret_cast<const uint4*>(a.add + off), f, (const bf16_t*)nullptr);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] += f[e];
+  }
+  *reinterpret_cast<uint4*>(a.y + off) = f_to_chunk(acc, (const bf16_t*)nullptr);
+}
+template <int ST>
+constexpr int kDwRun = ST == 1 ? 8 : 4;  // output rows per work item
+// y[n][p][q][c] = sum_tap x[n][p ST - 1 + r][q ST - 1 + s][c] w[tap][c]
+template <int ST>
+__device__ __forceinline__ void dw_direct_body(const DwArgs& a) {
+  constexpr int PR = kDwRun<ST>, NR = (PR - 1) * ST + 3;
+  const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
+  const int chunk = (int)(gt % (uint32_t)a.nchunk);  // (gridDim.x * blockDim.x is a multiple of nchunk)
+  float wf[9][8];
+  dw_load_w(a, chunk, wf);
+  const int64_t cs = a.C;
+  for (uint32_t it = gt; it < a.items; it += gridDim.x * blockDim.x) {
+    uint32_t n;
+    int pr, q;
+    dw_item(a, it, n, pr, q);
+    const int p0 = pr * PR;
+    const int pend = min(p0 + PR, a.P);                // (outputs p0 .. pend - 1)
+    const int hend = min(a.H, (pend - 1) * ST + 2);    // (input rows below hend)
+    const int h0 = p0 * ST - 1, w0 = q * ST - 1;
+    const bf16_t* img = a.x + (int64_t)n * a.H * a.W * cs + chunk * 8;
+    float acc[PR][8];
+#pragma unroll
+    for (int j = 0; j < PR; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[j][e] = 0.f;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+      const int h = h0 + i;
+      if (h >= 0 && h < hend) {
+        float xf[3][8];
+        dw_load3(img + (int64_t)h * a.W * cs, w0, a.W, cs, xf);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          if (i - r < 0 || (i - r) % ST || (i - r) / ST >= PR) continue;
+          const int j = (i - r) / ST;
+#pragma unroll
+          for (int s = 0; s < 3; ++s)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[j][e] = fmaf(xf[s][e], wf[r * 3 + s][e], acc[j][e]);
+        }
+      }
+      if (i >= 2 && (i - 2) % ST == 0) {  // output row (i - 2) / ST has its three tap rows
+        const int j = (i - 2) / ST;
+        if (p0 + j < pend) dw_store(a, (((int64_t)n * a.P + p0 + j) * a.Q + q) * cs + chunk * 8, acc[j]);
+      }
+    }
+  }
+}
+template <int ST>
+__global__ __launch_bounds__(256) void dwconv_fwd_kernel(DwArgs a) {
+  dw_direct_body<ST>(a);
+}
+// Data gradient. Stride 1: the forward form over dy with the mirrored taps, dx[h] = sum dy[h + t - 1]
+// w[8 - t]. Stride 2, a gather: dx[h][w] sums the taps (r, s) with h + 1 - r and w + 1 - s even, dy[(h + 1
+// - r) / 2][(w + 1 - s) / 2] w[r][s] -- an even row takes tap row 1, an odd one rows 2 and 0 (1, 2 or 4
+// taps in all). A work item is one dx column of a run of 8 dx rows from an even row: its 5 dy rows are
+// loaded once, 1 (even column) or 2 (odd) chunks each; the lane selects its column parity's taps once per
+// item. The compact copy is the mirrored one (tap 8 - t holds tap t) in both forms.
+template <int ST>
+__global__ __launch_bounds__(256) void dwconv_dgrad_kernel(DwArgs a) {
+  if constexpr (ST == 1) {
+    dw_direct_body<1>(a);
+  } else {
+    constexpr int PR = 8, ND = PR / 2 + 1;
+    const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
+    const int chunk = (int)(gt % (uint32_t)a.nchunk);
+    float wf[9][8];
+    dw_load_w(a, chunk, wf);
+    const int64_t cs = a.C;
+    for (uint32_t it = gt; it < a.items; it += gridDim.x * blockDim.x) {
+      uint32_t n;
+      int pr, w;
+      dw_item(a, it, n, pr, w);
+      const int h0 = pr * PR;  // (even); a.H x a.W is dy, a.P x a.Q is dx
+      const bool odd = w & 1;
+      const int ca = (w + 1) >> 1, cb = (w - 1) >> 1;  // dy columns of tap column (odd ? 0 : 1) and 2
+      float wa[3][8], wb[3][8];
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          wa[r][e] = odd ? wf[8 - r * 3][e] : wf[8 - (r * 3 + 1)][e];
+          wb[r][e] = odd ? wf[8 - (r * 3 + 2)][e] : 0.f;
+        }
+      const bf16_t* img = a.x + (int64_t)n * a.H * a.W * cs + chunk * 8;
+      float acc[PR][8];
+#pragma unroll
+      for (int j = 0; j < PR; ++j)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[j][e] = 0.f;
+#pragma unroll
+      for (int i = 0; i < ND; ++i) {
+        const int py = (h0 >> 1) + i;
+        if (py < a.H && 2 * py - 1 < a.P) {
+          const bf16_t* row = img + (int64_t)py * a.W * cs;
+          float fa[8], fb[8];
+          chunk_to_f(ca < a.W ? *reinterpret_cast<const uint4*>(row + (int64_t)ca * cs) : make_uint4(0, 0, 0, 0), fa,
+                     (const bf16_t*)nullptr);
+          chunk_to_f(odd && cb < a.W ? *reinterpret_cast<const uint4*>(row + (int64_t)cb * cs) : make_uint4(0, 0, 0, 0),
+                     fb, (const bf16_t*)nullptr);
+#pragma unroll
+          for (int r = 2; r >= 0; --r) {  // dx row 2 py - 1 + r
+            const int j = 2 * i - 1 + r;
+            if (j < 0 || j >= PR) continue;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[j][e] = fmaf(fb[e], wb[r][e], fmaf(fa[e], wa[r][e], acc[j][e]));
+          }
+        }
+#pragma unroll
+        for (int j = 2 * i - 1; j <= 2 * i; ++j)  // rows 2 i - 1 and 2 i are complete
+          if (j >= 0 && j < PR && h0 + j < a.P)
+            dw_store(a, (((int64_t)n * a.P + h0 + j) * a.Q + w) * cs + chunk * 8, acc[j]);
+      }
+    }
+  }
+}
+// Weight gradient: dw[c][tap] = sum over n, p, q of x[n][p ST - 1 + r][q ST - 1 + s][c] dy[n][p][q][c]. The same
+// work items over dy; a lane keeps its chunk's 8 channels x 9 taps of fp32 sums over all its items (each x
+// row of a run loaded once, multiplied with the up to three dy rows it is a tap row of). The workgroup's
+// lanes of one chunk are summed through LDS in lane order and the workgroup stores its [C][9] partial into
+// the split-M slab with plain stores (launch_slab_reduce adds the slabs into dw: no float atomics, the same
+// bits every run).
+constexpr int kDwWgradThreads = 768;  // 12 waves: one workgroup fills a CU's 3 waves per SIMD (~150 VGPRs)
+template <int ST>
+__global__ __launch_bounds__(kDwWgradThreads) void dwconv_wgrad_kernel(DwArgs a) {
+  constexpr int PR = kDwRun<ST>, NR = (PR - 1) * ST + 3;
+  __shared__ float red[18][kDwWgradThreads];
+  const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
+  const int chunk = (int)(gt % (uint32_t)a.nchunk);
+  const int64_t cs = a.C;
+  float acc[9][8];
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[t][e] = 0.f;
+  for (uint32_t it = gt; it < a.items; it += gridDim.x * blockDim.x) {
+    uint32_t n;
+    int pr, q;
+    dw_item(a, it, n, pr, q);
+    const int p0 = pr * PR;
+    const int pend = min(p0 + PR, a.P);
+    const int hend = min(a.H, (pend - 1) * ST + 2);
+    const int h0 = p0 * ST - 1, w0 = q * ST - 1;
+    const bf16_t* img = a.x + (int64_t)n * a.H * a.W * cs + chunk * 8;
+    const bf16_t* gy = a.dy + (((int64_t)n * a.P + p0) * a.Q + q) * cs + chunk * 8;
+    float dyf[PR][8];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+      if (i % ST == 0 && i / ST < PR) {  // dy row p0 + i / ST: first needed by this x row (its tap row 0)
+        const int j = i / ST;
+        chunk_to_f(p0 + j < pend ? *reinterpret_cast<const uint4*>(gy + (int64_t)j * a.Q * cs) : make_uint4(0, 0, 0, 0),
+                   dyf[j], (const bf16_t*)nullptr);
+      }
+      const int h = h0 + i;
+      if (h >= 0 && h < hend) {
+        float xf[3][8];
+        dw_load3(img + (int64_t)h * a.W * cs, w0, a.W, cs, xf);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          if (i - r < 0 || (i - r) % ST || (i - r) / ST >= PR) continue;
+          const int j = (i - r) / ST;
+#pragma unroll
+          for (int s = 0; s < 3; ++s)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[r * 3 + s][e] = fmaf(xf[s][e], dyf[j][e], acc[r * 3 + s][e]);
+        }
+      }
+    }
+  }
+  // lanes tid = t0, t0 + nchunk, ... of this workgroup hold chunk (base + t0) % nchunk; four passes of 2 channels
+  const int base = (int)((blockIdx.x * blockDim.x) % (uint32_t)a.nchunk);
+  float* out = a.slab + (int64_t)blockIdx.x * a.C * 9;
+#pragma unroll
+  for (int part = 0; part < 4; ++part) {
+    if (part) __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+      for (int t = 0; t < 9; ++t) red[e * 9 + t][threadIdx.x] = acc[t][2 * part + e];
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < a.nchunk * 18; idx += blockDim.x) {
+      const int ck = idx / 18, k = idx - ck * 18;
+      float sum = 0.f;
+      for (int t = (ck - base + a.nchunk) % a.nchunk; t < (int)blockDim.x; t += a.nchunk) sum += red[k][t];
+      out[(ck * 8 + 2 * part + k / 9) * 9 + k % 9] = sum;
+    }
+  }
+}
+// compact compute copy of a depthwise convolution: out[tap][c] = w[c][mirror ? 8 - tap : tap]
+__global__ void pack_dw_kernel(const float* __restrict__ wm, bf16_t* __restrict__ out, int C, int mirror) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < 9 * C; i += gridDim.x * blockDim.x) {
+    const int t = i / C, c = i - t * C;
+    out[i] = f2bf(wm[c * 9 + (mirror ? 8 - t : t)]);
+  }
+}
+
+// Does the grouped convolution d run the depthwise kernels (forward and data gradient; the weight gradient:
+// dw_wgrad_shape below)? Measured on MobileNet 1.0 at batch 256 (tools/conv_bench.py): every
+// forward and data gradient 1.35-3.1x faster than the block-diagonal tiles.
+bool dw_shape(const rn_conv_desc* d) {
+  if (!d || d->dtype != RN_BF16 || d->groups <= 1) return false;
+  if (d->groups != d->c || d->k != d->c || d->c != d->c_real || d->k_pad != d->k) return false;
+  if (d->r != 3 || d->s != 3 || d->pad_h != 1 || d->pad_w != 1 || d->stride_h != d->stride_w) return false;
+  if (d->stride_h != 1 && d->stride_h != 2) return false;
+  return d->c % 8 == 0 && d->c <= 1024;
+}
+// recorded in the descriptor by rn_conv_desc_init as grouped_direct = 2 (rn_set_tuning 28 = 1 at that time:
+// the block-diagonal path), as gd_direct_ok's 1
+bool dw_ok(const rn_conv_desc* d) { return d && d->grouped_direct == 2 && dw_shape(d); }
+// The weight gradient of a depthwise descriptor on dwconv_wgrad_kernel? (It reads no compute copy, so the
+// choice is free per shape.) Excluded: stride 2 over 14 x 14 x 512 (conv_13_dw) -- 34.4 / 34.5 us against
+// 30.4 / 30.6 us on the block-diagonal gdiag tile: 256 x 7 x 7 outputs leave each lane one short work item
+// while every workgroup still stores and reduces its 18 KB partial. Every other shape: 1.12-2.96x faster.
+bool dw_wgrad_shape(const rn_conv_desc* d) {
+  return !(d->stride_h == 2 && d->c == 512 && d->h * d->w <= 14 * 14);
+}
+
+// geometry of a depthwise launch (mode 0 forward, 1 data gradient, 2 weight gradient): a's shape fields and
+// the workgroups of `threads` lanes -- a whole number of chunk periods (threads * workgroups % nchunk == 0), at
+// most `cap` rounded up to that (rn_set_tuning 28 >= 2: that many, to exercise the work-item loop on small
+// tensors)
+int dw_geometry(const rn_conv_desc* d, int mode, DwArgs& a, int cap, int threads = 256) {
+  a.C = d->c;
+  a.nchunk = d->c / 8;
+  int run;
+  if (mode == 1) { a.H = d->p; a.W = d->q; a.P = d->h; a.Q = d->w; run = 8; }
+  else { a.H = d->h; a.W = d->w; a.P = d->p; a.Q = d->q; run = d->stride_h == 1 ? 8 : 4; }
+  a.pb = (a.P + run - 1) / run;
+  const int64_t items = (int64_t)d->n * a.pb * a.Q * a.nchunk;
+  a.items = (uint32_t)std::min<int64_t>(items, INT32_MAX);
+  a.fdC = make_fastdiv(a.nchunk); a.fdQ = make_fastdiv(a.Q); a.fdPB = make_fastdiv(a.pb);
+  if (g_tune[RN_TUNE_DEPTHWISE] >= 2) cap = g_tune[RN_TUNE_DEPTHWISE];
+  int gcd = a.nchunk;
+  for (int t = threads % gcd; t; ) { const int u = gcd % t; gcd = t; t = u; }
+  const int period = a.nchunk / gcd;
+  const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((items + threads - 1) / threads, cap));
+  return (int)((blocks + period - 1) / period * period);
+}
+int dw_launch(const rn_conv_desc* d, int mode, const void* x, const void* w, void* y, const void* add,
+              hipStream_t st) {
+  DwArgs a{};
+  a.x = (const bf16_t*)x; a.w = (const bf16_t*)w; a.y = (bf16_t*)y; a.add = (const bf16_t*)add;
+  // (3 workgroups of 4 waves per CU: the kernels' ~150 VGPRs hold 3 waves per SIMD, one resident round)
+  const int blocks = dw_geometry(d, mode, a, 3 * chip_cus());
+  RN_CHECK_ARG((int64_t)d->n * a.pb * a.Q * a.nchunk < INT32_MAX, "depthwise: tensor too large");
+  if (mode == 0) {
+    if (d->stride_h == 1) hipLaunchKernelGGL(dwconv_fwd_kernel<1>, dim3(blocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(dwconv_fwd_kernel<2>, dim3(blocks), dim3(256), 0, st, a);
+    return rn_check_launch("dwconv_fwd");
+  }
+  if (d->stride_h == 1) hipLaunchKernelGGL(dwconv_dgrad_kernel<1>, dim3(blocks), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(dwconv_dgrad_kernel<2>, dim3(blocks), dim3(256), 0, st, a);
+  return rn_check_launch("dwconv_dgrad");
+}
+
 // conv3x3c64_band_kernel for these arguments? (rn_set_tuning 26 = 1: never -- the implicit-GEMM tile)
 bool band_ok(const rn_conv_desc* d) {
   return g_tune[RN_TUNE_CONV_BAND] != 1 && d->dtype == RN_BF16 && d->groups <= 1 && d->r == 3 && d->s == 3 &&
@@ -4351,6 +4663,7 @@ int rn_conv_desc_init(rn_conv_desc* d) {
   d->q = (d->w + 2 * d->pad_w - d->s) / d->stride_w + 1;
   RN_CHECK_ARG(d->p > 0 && d->q > 0, "empty output");
   d->grouped_direct = (g_tune[RN_TUNE_GROUP_DIRECT] != 1 && gd_direct_shape(d, 0)) ? 1 : 0;
+  if (g_tune[RN_TUNE_DEPTHWISE] != 1 && dw_shape(d)) d->grouped_direct = 2;  // (the depthwise kernels)
   RN_CHECK_ARG((int64_t)d->n * d->h * d->w < (1ll << 31) && (int64_t)d->n * d->p * d->q < (1ll << 31),
                "too many pixels");
   return 0;
@@ -4363,6 +4676,7 @@ int64_t rn_conv_weight_numel(const rn_conv_desc* d) {
 int64_t rn_conv_pack_numel(const rn_conv_desc* d, int32_t which) {
   const int64_t RS = (int64_t)d->r * d->s;
   if (gd_direct_ok(d, which)) return (int64_t)d->c * 9 * (d->c / d->groups);  // (compact, see rn.h)
+  if (dw_ok(d)) return (int64_t)9 * d->c;  // ([tap][c], see rn.h)
   if (d->groups > 1) {
     const int cpg = d->c / d->groups, kpg = d->k / d->groups;
     return which == 0 ? d->k * RS * group_blk(kpg, cpg) : d->c * RS * group_blk(cpg, kpg);
@@ -4379,6 +4693,10 @@ int rn_conv_fwd_x(const rn_conv_desc* d, const void* x, const void* w, void* y, 
   if (gd_direct_ok(d, 0)) {
     RN_CHECK_ARG(!bias && !part && y_dtype == RN_BF16, "grouped direct forward: no bias / statistics, bf16 output");
     return gd_launch(d, 0, x, w, y, add_src, as_stream(stream));
+  }
+  if (dw_ok(d)) {
+    RN_CHECK_ARG(!bias && !part && y_dtype == RN_BF16, "depthwise forward: no bias / statistics, bf16 output");
+    return dw_launch(d, 0, x, w, y, add_src, as_stream(stream));
   }
   if (band_ok(d) && !add_src && !bias && !part && y_dtype == RN_BF16)
     return band_launch(d, x, w, y, 0, as_stream(stream), in_scale, in_shift);
@@ -4450,7 +4768,7 @@ int rn_conv_fwd_bnstats(const rn_conv_desc* d, const void* x, const void* w, voi
 
 int32_t rn_conv_tile(const rn_conv_desc* d, int32_t mode) {
   if (d && mode == 2 && d->groups <= 1) return i8_tile_cols(make_igemm_args(d, 0));  // int8 forward
-  if (!d || d->dtype != RN_BF16 || (mode != 0 && mode != 1) || gd_direct_ok(d, mode)) return 0;
+  if (!d || d->dtype != RN_BF16 || (mode != 0 && mode != 1) || gd_direct_ok(d, mode) || dw_ok(d)) return 0;
   const IgemmArgs a = make_igemm_args(d, mode);
   const int64_t xb = (int64_t)a.N * a.H * a.W * a.C * 2, wb = (int64_t)a.K * a.wrow * 2;
   return big_tile_cols(a, xb, wb);
@@ -4500,6 +4818,10 @@ int rn_conv_bwd_data_bnred_clip(const rn_conv_desc* d, const void* dy, const voi
     r.bnred = part; r.bn_x = (const bf16_t*)bn_x; r.bn_mean = bn_mean; r.bn_sc = bn_scale; r.bn_sh = bn_shift;
     r.bn_relu = relu;
     return gd_launch(d, 1, dy, w_crsk, dx, add_src, as_stream(stream), &r);
+  }
+  if (dw_ok(d)) {
+    RN_CHECK_ARG(dx && !part && !clip, "depthwise data gradient: dx required, no BN reduction");
+    return dw_launch(d, 1, dy, w_crsk, dx, add_src, as_stream(stream));
   }
   if (band_ok(d) && !part && !add_src && !clip && dx) return band_launch(d, dy, w_crsk, dx, 1, as_stream(stream));
   // (with the BN reduction only: the plain form -- epilogue 0, kept in the kernel for tests -- measured slower
@@ -4590,6 +4912,27 @@ int wgrad_dispatch(const rn_conv_desc* d, const void* x, const void* dy, float* 
   a.cblk = d->c;
   a.creal = d->c_real;
   const bool grouped = d->groups > 1;
+  // depthwise: dwconv_wgrad_kernel, one [c][9] partial per workgroup into the slab (needed in every mode:
+  // the kernel has no atomic form)
+  if (dw_ok(d) && dw_wgrad_shape(d)) {
+    RN_CHECK_ARG(!in_scale && !i8, "depthwise weight gradient: no input transform, no int8 codes");
+    DwArgs g{};
+    const int blocks = dw_geometry(d, 2, g, 2 * wgrad_cus(), kDwWgradThreads);
+    const int64_t n = (int64_t)9 * d->c, need = blocks * n * 4;
+    if (ws_need) *ws_need = need;
+    if (!launch) return 0;
+    RN_CHECK_ARG((int64_t)d->n * g.pb * g.Q * g.nchunk < INT32_MAX, "depthwise: tensor too large");
+    if (!ws || ws_bytes < need) {
+      rn_set_error("deterministic weight gradients need the split-M workspace (rn_conv_wgrad_ws_bytes)");
+      return -1;
+    }
+    g.x = (const bf16_t*)x; g.dy = (const bf16_t*)dy; g.slab = ws;
+    if (d->stride_h == 1) hipLaunchKernelGGL(dwconv_wgrad_kernel<1>, dim3(blocks), dim3(kDwWgradThreads), 0, st, g);
+    else hipLaunchKernelGGL(dwconv_wgrad_kernel<2>, dim3(blocks), dim3(kDwWgradThreads), 0, st, g);
+    if (rn_check_launch("dwconv_wgrad")) return -1;
+    launch_slab_reduce(ws, blocks, n, dw, st);
+    return rn_check_launch("wgrad_slab_reduce");
+  }
   if (grouped) {
     a.grouped = 1;
     a.gk = d->k / d->groups; a.gc = d->c / d->groups;
@@ -5252,6 +5595,11 @@ int rn_conv_weight_pack(const rn_conv_desc* d, const float* wm, void* w_krsc, vo
     for (int which = 0; which < 2; ++which) {
       void* out = which == 0 ? w_krsc : w_crsk;
       if (!out) continue;
+      if (dw_ok(d)) {
+        hipLaunchKernelGGL(pack_dw_kernel, dim3(grid_for((int64_t)9 * d->c)), dim3(256), 0, st, wm, (bf16_t*)out, d->c,
+                           which);
+        continue;
+      }
       if (gd_direct_ok(d, which)) {
         hipLaunchKernelGGL(pack_group_direct_kernel, dim3(grid_for((int64_t)d->c * 9 * cpg)), dim3(256), 0, st, wm,
                            (bf16_t*)out, d->c, cpg, which);
@@ -5334,8 +5682,12 @@ int rn_conv_weight_pack_multi(const rn_conv_desc* descs, const float* const* w_m
       p.transpose = which;
       p.cpg = cpg;
       p.rs = d->r * d->s;
-      p.direct = gd_direct_ok(d, which) ? 1 : 0;
-      if (p.direct) {
+      p.direct = dw_ok(d) ? 2 : gd_direct_ok(d, which) ? 1 : 0;
+      if (p.direct == 2) {  // depthwise: [tap][c]
+        p.ncols = d->c;
+        p.total = (int64_t)9 * d->c;
+        p.cblk = p.gcol = p.gred = 0;
+      } else if (p.direct) {
         p.ncols = d->c;
         p.total = (int64_t)d->c * 9 * cpg;
         p.cblk = p.gcol = p.gred = 0;

@@ -976,7 +976,8 @@ class Executor:
                 if op.kind == "bn" and not op.use_global_stats:
                     src = producer.get(id(op.x))
                     if src is not None and src.kind == "conv" and src.y.c % 8 == 0 and src.y.cp == op.x.cp and \
-                            (stats_mode == "2" or self._big_tile(src, 0) or self._grouped_fuse(src, 0)):
+                            (stats_mode == "2" or self._big_tile(src, 0) or self._grouped_fuse(src, 0)) and \
+                            not self._depthwise(src):
                         src.bnstats = True
                         op.part_src = src
                     elif src is not None and src.kind == "stem" and src.y.cp == op.x.cp and \
@@ -1344,6 +1345,16 @@ class Executor:
             return True
         return int(self.lib.rn_conv_tile(L.C.byref(d), mode)) == 64
 
+    def _depthwise(self, op):
+        """Does conv `op` run the depthwise kernels (grouped_direct = 2)? They carry no BatchNorm fusion: the
+        BatchNorm after a depthwise conv runs its own statistics pass and rn_bn_bwd, whatever the fusion
+        switches say."""
+        if op.kind != "conv" or op.groups <= 1 or self.lib is None:
+            return False
+        x, y = op.x, op.y
+        d = self._conv_desc(x.n, x.h, x.w, x.cp, x.c, y.c, op.kernel, op.stride, op.pad, op.groups)
+        return d.grouped_direct == 2
+
     def _conv_fwd_call(self, op, d, xptr, res, sp, stats=True):
         """Conv forward; emits the next BatchNorm's statistics when one consumes y (training), and
         applies the producing BatchNorm+ReLU on load when that BN is fused (op.xf)."""
@@ -1679,6 +1690,7 @@ class Executor:
                 elif bwd_fusion and not op.desc.dy2 and w and w[0] == "dgrad" and dy is w[4] and \
                         op.y.c % 8 == 0 and op.y.c == op.y.cp and \
                         (bwd_all or self._big_tile(w[2], 1) or self._grouped_fuse(w[2], 1)) and \
+                        not self._depthwise(w[2]) and \
                         (not op.desc.clip or self._big_tile(w[2], 1)):  # (the clip: bf16 LDS-DMA tiles)
                     # the conv dgrad that completes this BN's output gradient also reduces its backward
                     # (sum dz, sum dz*(x - mean)); the BN then needs only finalize + apply

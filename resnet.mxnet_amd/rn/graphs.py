@@ -7,6 +7,7 @@ the reference function it mirrors, so checkpoints and parity fixtures are interc
   resnet_cifar10(...)  <-> symbol/resnet.py:123-148  (post-activation basic units)
   resnext(...)         <-> symbol/resnext.py:72-103  (grouped 3x3, BN on the shortcut)
   resnet_int8(...)     <-> symbol/resnet_int8.py:69-131 + int8_api.py:120-171 (fake-quant QAT)
+  mobilenet(...)       <-> symbol/mobilenet.py:38-144    (MobileNet-v1: depthwise 3x3 + pointwise 1x1)
 The equivalence is checked against parameter counts and names restated from the reference
 (tests/test_symbol_plan.py) -- the reference files themselves are never imported.
 """
@@ -218,6 +219,51 @@ def resnet_int8(units, num_stage, filter_list, num_classes, data_type="float32",
     flat = mx.sym.Flatten(data=pool1)
     fc1 = quant_fc("fc1", flat, num_classes, c, **qkw)
     return mx.sym.SoftmaxOutput(data=fc1, name="softmax")
+
+
+# ----------------------------------------------------------------------------- MobileNet-v1
+MOBILENET_ALPHAS = [0.25, 0.50, 0.75, 1.0]
+# (depth multiplier of the depthwise 3x3 layer conv_N_dw, its stride, multiplier of the pointwise conv_N) for
+# N = 2 .. 14, in units of base = int(32 * alpha) -- symbol/mobilenet.py:95-137
+_MOBILENET_LAYERS = [(1, 1, 2), (2, 2, 4), (4, 1, 4), (4, 2, 8), (8, 1, 8), (8, 2, 16), (16, 1, 16), (16, 1, 16),
+                     (16, 1, 16), (16, 1, 16), (16, 1, 16), (16, 2, 32), (32, 1, 32)]
+
+
+def _mobilenet_conv(x, name, nf, kernel=(1, 1), stride=(1, 1), pad=(0, 0), num_group=1):
+    """symbol/mobilenet.py:38-42 Conv: Convolution -> BatchNorm(fix_gamma=True, MXNet's default eps 1e-3 and
+    momentum 0.9) -> relu, named <name>_conv2d / _batchnorm / _relu."""
+    conv = mx.sym.Convolution(data=x, num_filter=nf, kernel=kernel, num_group=num_group, stride=stride, pad=pad,
+                              no_bias=True, name="%s_conv2d" % name)
+    bn = mx.sym.BatchNorm(data=conv, name="%s_batchnorm" % name, fix_gamma=True)
+    return mx.sym.Activation(data=bn, act_type="relu", name="%s_relu" % name)
+
+
+def mobilenet(num_classes, alpha=1, resolution=224, **kwargs):
+    """symbol/mobilenet.py:85-144: conv_1 (3x3 / stride 2), 13 depthwise-separable pairs, a windowed
+    (resolution / 32)^2 average pool, fc, softmax."""
+    assert alpha in MOBILENET_ALPHAS, "Invalid alpha=[{0}], must be one of [{1}]".format(alpha, MOBILENET_ALPHAS)
+    assert resolution % 32 == 0, "resolution must be multiple of 32"
+    base = int(32 * alpha)
+    body = _mobilenet_conv(mx.sym.Variable(name="data"), "conv_1", base, (3, 3), (2, 2), (1, 1))
+    for i, (dw, stride, pw) in enumerate(_MOBILENET_LAYERS):
+        body = _mobilenet_conv(body, "conv_%d_dw" % (i + 2), base * dw, (3, 3), (stride, stride), (1, 1),
+                               num_group=base * dw)
+        body = _mobilenet_conv(body, "conv_%d" % (i + 2), base * pw)
+    pool_size = int(resolution / 32)
+    pool = mx.sym.Pooling(data=body, kernel=(pool_size, pool_size), stride=(1, 1), pool_type="avg",
+                          name="global_pool")
+    flatten = mx.sym.Flatten(data=pool, name="flatten")
+    fc = mx.sym.FullyConnected(data=flatten, num_hidden=num_classes, name="fc")
+    return mx.sym.SoftmaxOutput(data=fc, name="softmax")
+
+
+def get_symbol_compact(num_classes, alpha=1, resolution=224, **kwargs):
+    """symbol/mobilenet.py:51-82: the same graph as mobilenet(), written there with a helper."""
+    return mobilenet(num_classes, alpha=alpha, resolution=resolution, **kwargs)
+
+
+def mobilenet_1_0(num_classes=1000):
+    return mobilenet(num_classes, alpha=1, resolution=224)
 
 
 def resnet50_int8(num_classes=1000):
