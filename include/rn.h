@@ -78,6 +78,11 @@ int32_t rn_conv_bn_part_rows(const rn_conv_desc* d, int32_t mode);
  * 128-row kernel. Lets a caller enable the BatchNorm epilogue fusions only where they pay (the
  * 64-column tile has none: with a fused epilogue those layers run the 128-row kernel). */
 int32_t rn_conv_tile(const rn_conv_desc* d, int32_t mode);
+/* 1 where the data gradient of `d` with a BatchNorm epilogue (rn_conv_bwd_data_bnred, its reduction-only
+ * form, rn_conv_bwd_data_bnapply) runs the streaming kernel: bf16, dense 1x1 stride 1 without padding,
+ * k = 64 or 128 unpadded, c a multiple of 128, n h w c 2 bytes below 2^31 (rn_set_tuning 27 = 1: never).
+ * 0 otherwise (the tiles). A caller takes the recomputed BatchNorm backward only there. */
+int32_t rn_conv_dgrad_streamed(const rn_conv_desc* d);
 /* Int8 forward of a quantized convolution (resnet_int8 / attach_quantize_node graphs: conv over
  * Quantization_int8(data) and Quantization_int8(weight), symbol/int8_api.py:120-151). x_codes /
  * w_codes are the int8 codes (value = code * unit; NHWC / KRSC, channel stride d->c bytes, a multiple

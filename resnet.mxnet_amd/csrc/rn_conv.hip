@@ -4409,9 +4409,15 @@ struct D1Args {
 // ADD: p.add is set (a compile-time branch: with a runtime one, hipcc (ROCm 7.2) let the epilogue's first VALU
 // read an MFMA result across the branch without the wait states it needs -- stale values in 1 of 8 channels,
 // run to run). NH: 32-channel halves per wave (NH = 2: a lane's two 16-byte chunks of a row are 64 bytes apart,
-// so each row's 128-byte lines are written whole by one wave).
+// so each row's 128-byte lines are written whole by one wave). The apply form (EPI 3) at NH = 2 has 96 per-channel
+// constants per lane, more than the registers hold beside the weights (60 to 216 VGPRs spilled): the workgroup's
+// 256 channels' A, mean dz, A2 and mean then sit in LDS ([4][256] floats, filled once), each step reads its lane's
+// chunks of them with 16-byte LDS reads, and only scale / shift stay in registers (DESIGN.md has the table; with
+// scale / shift in LDS too it measured the same or 1 % slower).
 template <int KS, int EPI, int ADD, int NH>
 __global__ __launch_bounds__(256, 2) void dgrad1x1_stream_kernel(D1Args p) {
+  constexpr bool kLds = EPI == 3 && NH == 2;
+  __shared__ __attribute__((aligned(16))) float cst[4 * 256];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int g = lane >> 4, i = lane & 15;
   const int lid = xcd_remap(blockIdx.x, gridDim.x);
@@ -4445,11 +4451,17 @@ __global__ __launch_bounds__(256, 2) void dgrad1x1_stream_kernel(D1Args p) {
         sc[h][e] = p.bn_sc[c];
         sh[h][e] = p.bn_sh[c];
       }
-      if constexpr (EPI == 3) {
+      if constexpr (EPI == 3 && !kLds) {
         const float4 cf = reinterpret_cast<const float4*>(p.coef)[c];
         ca[h][e] = cf.x; cm[h][e] = cf.y; c2[h][e] = cf.z; mu[h][e] = cf.w;
       }
     }
+  if constexpr (kLds) {  // thread t: channel 256 cg + t (ncg = C / 256 here)
+    const int c = cg * 256 + tid;
+    const float4 cf = reinterpret_cast<const float4*>(p.coef)[c];
+    cst[tid] = cf.x; cst[256 + tid] = cf.y; cst[512 + tid] = cf.z; cst[768 + tid] = cf.w;
+    __syncthreads();
+  }
   const uint4 z4 = make_uint4(0, 0, 0, 0);
   // buffer loads (a row past the block reads zeros through an offset past the buffer): no pointer selects,
   // which hipcc turns into flat loads whose waits (vmcnt(0) with lgkmcnt) would also drain this step's stores
@@ -4524,14 +4536,31 @@ __global__ __launch_bounds__(256, 2) void dgrad1x1_stream_kernel(D1Args p) {
       chunk_to_f(a0[h], af, (const bf16_t*)nullptr);
       uint4 out;
       if constexpr (EPI == 3) {
-        float gv[8];
+        float gv[8], ka[8], km[8], k2[8], ku[8];
+        if constexpr (kLds) {
+          // this chunk's constants from LDS, through an offset hipcc cannot see through: it would merge the 14
+          // steps' reads of the same words into one and keep all of them in registers again
+          int lo = wid * 64 + 32 * h + 8 * g;
+          asm volatile("" : "+v"(lo));
+          auto l8 = [&](int j, float (&o)[8]) __attribute__((always_inline)) {
+            const float4 a = *reinterpret_cast<const float4*>(&cst[j * 256 + lo]);
+            const float4 b = *reinterpret_cast<const float4*>(&cst[j * 256 + lo + 4]);
+            o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+          };
+          l8(0, ka); l8(1, km); l8(2, k2); l8(3, ku);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            ka[e] = ca[h][e]; km[e] = cm[h][e]; k2[e] = c2[h][e]; ku[e] = mu[h][e];
+          }
+        }
         chunk_to_f(f_to_chunk(v, (const bf16_t*)nullptr), gv, (const bf16_t*)nullptr);  // the gradient as stored
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float dz = norelu ? gv[e] : gv[e] * (fmaf(xf[e], sc[h][e], sh[h][e]) > 0.f ? 1.f : 0.f);
           // spelled out as bn_bwd_apply_kernel is compiled (fma(A, dz - mean dz, -(A2 (x - mean)))): bit-identical
-          const float q = c2[h][e] * (xf[e] - mu[h][e]);
-          float w = fmaf(ca[h][e], dz - cm[h][e], -q);
+          const float q = k2[e] * (xf[e] - ku[e]);
+          float w = fmaf(ka[e], dz - km[e], -q);
           if (ADD) w += af[e];
           v[e] = w;
         }
@@ -4593,7 +4622,7 @@ bool d1_stream_ok(const rn_conv_desc* d, const float* clip) {
          d->groups <= 1 && d->r == 1 &&
          d->s == 1 && d->stride_h == 1 && d->stride_w == 1 && d->pad_h == 0 && d->pad_w == 0 &&
          d->c == d->c_real && d->c % 128 == 0 && d->k == d->k_pad && (d->k == 64 || d->k == 128) &&
-         (int64_t)d->n * d->h * d->w * d->c < INT32_MAX;
+         (int64_t)d->n * d->h * d->w * d->c * 2 <= INT32_MAX;  // (the buffer descriptors' byte counts are ints)
 }
 int d1_stream_launch(const rn_conv_desc* d, int epi, const void* dy, const void* w, void* dx, const void* add,
                      const void* bn_x, const float* mean, const float* coef, const float* sc, const float* sh,
@@ -4601,15 +4630,15 @@ int d1_stream_launch(const rn_conv_desc* d, int epi, const void* dy, const void*
   D1Args a{};
   a.dy = (const bf16_t*)dy; a.w = (const bf16_t*)w; a.dx = (bf16_t*)dx; a.add = (const bf16_t*)add;
   a.bn_x = (const bf16_t*)bn_x; a.bn_mean = mean; a.coef = coef; a.bn_sc = sc; a.bn_sh = sh; a.part = part;
-  // 64 channels per wave where C % 256 == 0 (rn_set_tuning 27 = 2: 32), except the apply form (EPI 3), whose
-  // per-channel coefficients need the registers
-  const int nh = (epi != 3 && d->c % 256 == 0 && g_tune[RN_TUNE_DGRAD_STREAM] != 2) ? 2 : 1;
+  // 64 channels per wave where C % 256 == 0 (rn_set_tuning 27 = 2: 32); the apply form (EPI 3) then reads its
+  // per-channel coefficients from LDS
+  const int nh = (d->c % 256 == 0 && g_tune[RN_TUNE_DGRAD_STREAM] != 2) ? 2 : 1;
   a.M = d->n * d->h * d->w; a.C = d->c; a.K = d->k; a.relu = relu; a.ncg = d->c / (128 * nh);
   const dim3 grid((unsigned)(ceil_div(a.M, 224) * a.ncg));
 #define RN_D1N(KSV, AV, NHV)                                                                                  \
   if (epi == 0) hipLaunchKernelGGL((dgrad1x1_stream_kernel<KSV, 0, AV, NHV>), grid, dim3(256), 0, st, a);    \
   else if (epi == 2) hipLaunchKernelGGL((dgrad1x1_stream_kernel<KSV, 2, AV, NHV>), grid, dim3(256), 0, st, a); \
-  else hipLaunchKernelGGL((dgrad1x1_stream_kernel<KSV, 3, AV, 1>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((dgrad1x1_stream_kernel<KSV, 3, AV, NHV>), grid, dim3(256), 0, st, a);
 #define RN_D1(KSV, AV)     \
   if (nh == 2) {           \
     RN_D1N(KSV, AV, 2)     \
@@ -4773,6 +4802,8 @@ int32_t rn_conv_tile(const rn_conv_desc* d, int32_t mode) {
   const int64_t xb = (int64_t)a.N * a.H * a.W * a.C * 2, wb = (int64_t)a.K * a.wrow * 2;
   return big_tile_cols(a, xb, wb);
 }
+
+int32_t rn_conv_dgrad_streamed(const rn_conv_desc* d) { return d && d1_stream_ok(d, nullptr) ? 1 : 0; }
 
 int32_t rn_conv_bn_part_rows(const rn_conv_desc* d, int32_t mode) {
   if (d && mode == 2) return rn_conv_tile(d, 2) == 64 ? 64 : 224;  // int8 forward: per wave row / tile

@@ -1459,6 +1459,25 @@ class Executor:
                               self.wgrad_ws_bytes, sp)
         return self._call("rn_conv_bwd_filter", L.C.byref(d), x, dy, dw, sp)
 
+    # the recomputed BN backward's size gate: measured cold per layer, the recomputed chain wins from
+    # 98 MiB up on both layer classes (stage 1's from 25 MiB) and loses or ties below (stage 2's class at 49 MiB: 2 %
+    # slower; both at 12 MiB and less)
+    RECOMPUTE_MIN_BYTES = 64 << 20
+
+    def _bn_recompute_ok(self, op, cop, cadd, min_bytes):
+        """May the BatchNorm `op`, whose output gradient the data gradient of conv `cop` completes, take its
+        backward from a recomputed dgrad (rn_conv_bwd_data_bnapply)? Where that dgrad is the streaming kernel
+        (rn_conv_dgrad_streamed: the pre-activation units' conv1 of stages 1 and 2, symbol/resnet.py:17-20, a 1x1
+        reduction over 64 or 128 channels into 4x as many) and the only writer of the gradient (no fan-in add: the
+        reduction-only pass takes none). On the 224-row tiles (stages 3 and 4) the stored path is faster. Only
+        where the gradient that is then never stored has at least `min_bytes` (None: never): a small one comes back
+        from the caches and the stored path measured as fast or faster."""
+        d = cop.desc
+        return (min_bytes is not None and op.y.numel * 2 >= min_bytes
+                and self.dtype == L.RN_BF16 and cadd is None and not op.desc.clip and op.y.c == d.c and cop.x is op.y
+                and int(self.lib.rn_conv_dgrad_streamed(L.C.byref(d))) == 1
+                and int(self.lib.rn_conv_tile(L.C.byref(d), 1)) >= 128)
+
     def _quant_groups(self):
         """{id(bn): (bn, [quant ops])} for the BatchNorm+ReLU outputs that only activation quantizers
         (Quantization_int8 of data, the int8 graph) read -- one, or two (symbol/resnet_int8.py: a stage's
@@ -1514,12 +1533,19 @@ class Executor:
         for op in plan.ops:
             if op.kind == "bn":
                 op.pre_part = None  # set by the residual add's fused ReLU backward (this build)
+                op.recomputed = False  # its backward applied by a recomputed dgrad (rn_conv_bwd_data_bnapply)
         bwd_fusion = os.environ.get("RN_BN_BWD_FUSION", "1") in ("1", "2")
         bwd_all = os.environ.get("RN_BN_BWD_FUSION", "1") == "2"
-        # (removed in round 6, each measured slower or neutral, their kernels kept and kernel-tested: the BN backward
-        # applied by a recomputed dgrad, RN_BN_BWD_RECOMPUTE -- rn_conv_bwd_data_bnapply; 19.78 vs 19.43 ms with the
-        # streamed conv1 data gradients --, and a quantizer pair's clips folded into the later data gradient,
-        # RN_QUANT_PAIR_FUSION -- rn_conv_bwd_data_bnred_clip2; C5 22.68 / 22.69 vs 22.69 / 22.68 ms)
+        # the BN backward applied by a recomputed streamed dgrad (rn_conv_bwd_data_bnapply, _bn_recompute_ok):
+        # RN_BN_BWD_RECOMPUTE=0 keeps the stored gradient everywhere, 1 recomputes every such layer whatever its
+        # size, unset those of at least RECOMPUTE_MIN_BYTES (DESIGN.md has the measurements)
+        rmode = os.environ.get("RN_BN_BWD_RECOMPUTE", "")
+        if rmode not in ("", "0", "1"):
+            raise L.RNError("RN_BN_BWD_RECOMPUTE=%r: 0, 1 or unset" % rmode)
+        recompute_min_bytes = {"": self.RECOMPUTE_MIN_BYTES, "0": None, "1": 0}[rmode]
+        # (removed in round 6, measured neutral, its kernel kept and kernel-tested: a quantizer pair's clips folded
+        # into the later data gradient, RN_QUANT_PAIR_FUSION -- rn_conv_bwd_data_bnred_clip2; C5 22.68 / 22.69 vs
+        # 22.69 / 22.68 ms)
         # one workspace for the weight gradients' split-M partial tiles (rn_conv_bwd_filter_ws),
         # sized for the largest layer. Shared safely because every call using it is a weight-gradient
         # call, and those all run in plan order on ONE stream (the side stream when it is on:
@@ -1697,7 +1723,29 @@ class Executor:
                     _, ci, cop, cdy, cout, cadd = w
                     op.bnred_blocks = int(self.lib.rn_conv_bnred_blocks(L.C.byref(cop.desc)))
                     op.bnred = self._zeros(op.bnred_blocks * op.y.cp * 2, self.torch.float32)
-                    if op.desc.clip:  # (a folded quantizer straight-through clip)
+                    if self._bn_recompute_ok(op, cop, cadd, recompute_min_bytes):
+                        # pass 1 only reduces (the BN-width gradient is never written), finalize, then the same
+                        # dgrad recomputed with the BN backward applied in its epilogue (bit-identical)
+                        op.coef = self._zeros(4 * op.y.cp, self.torch.float32)
+                        self._bwd[ci] = self._call("rn_conv_bwd_data_bnred", L.C.byref(cop.desc), self._p(cdy),
+                                                   self._p(cop.wc), None, None, self._p(self.act(x)), op.sm, op.sc,
+                                                   op.sh, int(op.relu), self._p(op.bnred), sp)
+                        self._bwd.append(self._call("rn_bn_bwd_finalize", L.C.byref(op.desc), self._p(op.bnred),
+                                                    op.bnred_blocks, self._pp(op.gamma), op.sm, op.si,
+                                                    self._gp(op.gamma), self._gp(op.beta), self._p(op.coef), sp))
+                        self._bwd.append(self._call("rn_conv_bwd_data_bnapply", L.C.byref(cop.desc), self._p(cdy),
+                                                    self._p(cop.wc), self._p(out), self._p(add), self._p(self.act(x)),
+                                                    self._p(op.coef), op.sc, op.sh, int(op.relu), sp))
+                        # the gradient of the BN's output is never stored: the buffer bound for it when conv1's data
+                        # gradient was planned is released here (this dgrad was its only writer, the BN its only
+                        # reader; no bound call holds its pointer any more) -- every reference: the buffer table,
+                        # the writer record and this loop's own names
+                        assert self._grads.get(id(cop.x)) is cout
+                        del self._grads[id(cop.x)]
+                        self._gw[id(op.y)] = ("other",)
+                        w = dy = cout = None
+                        op.recomputed = True
+                    elif op.desc.clip:  # (a folded quantizer straight-through clip)
                         self._bwd[ci] = self._call("rn_conv_bwd_data_bnred_clip", L.C.byref(cop.desc),
                                                    self._p(cdy), self._p(cop.wc), self._p(cout), self._p(cadd),
                                                    self._p(self.act(x)), op.sm, op.sc, op.sh, int(op.relu),
@@ -1707,10 +1755,11 @@ class Executor:
                                                    self._p(cop.wc), self._p(cout), self._p(cadd),
                                                    self._p(self.act(x)), op.sm, op.sc, op.sh, int(op.relu),
                                                    self._p(op.bnred), sp)
-                    self._bwd.append(self._call("rn_bn_bwd_part", L.C.byref(op.desc), self._p(op.bnred),
-                                                op.bnred_blocks, self._p(self.act(x)), self._p(dy), self._p(out),
-                                                self._p(add), self._pp(op.gamma), op.sm, op.si, op.sc, op.sh,
-                                                self._gp(op.gamma), self._gp(op.beta), wsp, sp))
+                    if not op.recomputed:
+                        self._bwd.append(self._call("rn_bn_bwd_part", L.C.byref(op.desc), self._p(op.bnred),
+                                                    op.bnred_blocks, self._p(self.act(x)), self._p(dy), self._p(out),
+                                                    self._p(add), self._pp(op.gamma), op.sm, op.si, op.sc, op.sh,
+                                                    self._gp(op.gamma), self._gp(op.beta), wsp, sp))
                 elif bwd_fusion and not op.desc.dy2 and not op.desc.clip and w and w[0] == "pool" and dy is w[4] and \
                         op.y.c == op.y.cp and self.dtype == BF16 and os.environ.get("RN_POOL_BN_FUSION", "1") == "1" and \
                         int(self.lib.rn_pool_bwd_bnred_blocks(L.C.byref(w[2].desc))) > 0:
@@ -1813,6 +1862,7 @@ class Executor:
                     self._bwd.append(self._call("rn_pool_bwd", L.C.byref(op.desc), self._p(dy), self._p(op.argmax),
                                                 self._p(out), self._p(add), sp))
                     self._gw[id(x)] = ("pool", len(self._bwd) - 1, op, dy, out, add)
+        self._gw = {}  # (the writer records hold gradient tensors and serve only while the plan is bound)
 
     # ------------------------------------------------------------------ update
     def _build_update(self):

@@ -3,6 +3,8 @@ graph (default ResNet-50 v2, batch 256, bf16) -- the inner loop for conv-kernel 
 
 python tools/conv_bench.py [--graph resnet50|resnext50|resnet50_int8|mobilenet] [--iters 20] [--only fwd,dgrad,wgrad]
 Prints one line per unique shape (count = occurrences per step) and the per-step totals.
+python tools/conv_bench.py --only dgbn,bnst,bnrc --cold --filter conv1: the BatchNorm backward chain behind each conv1
+data gradient, stored against recomputed (in the step these tensors are not cache-resident: time them cold).
 """
 import argparse
 import ctypes as C
@@ -18,7 +20,8 @@ def main():
     ap.add_argument("--graph", default="resnet50")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--only", default="fwd,dgrad,wgrad", help="modes among fwd, dgrad, wgrad, dgbn (dgrad + BN reduction)")
+    ap.add_argument("--only", default="fwd,dgrad,wgrad", help="modes among fwd, dgrad, wgrad, dgbn (dgrad + BN reduction), bnst / bnrc (the "
+                    "BN backward chain of a conv1 data gradient, stored / recomputed; run them with --cold)")
     ap.add_argument("--filter", default="")
     ap.add_argument("--cold", action="store_true", help="evict L2/MALL (write 512 MB) before every timed call")
     a = ap.parse_args()
@@ -76,14 +79,44 @@ def main():
             "dgbn": lambda: lib.rn_conv_bwd_data_bnred(C.byref(d), P(yv), P(wc), P(dx), None, P(x), P(bnv), P(bnv),
                                                        P(bnv), 1, P(bnpart), st),
         }
+        # the whole backward of the BatchNorm whose output gradient this data gradient is (the pre-activation
+        # units' bn1 -> conv1), with the fan-in add of the step: bnst = stored (dgrad + reduction, then
+        # rn_bn_bwd_part reads the gradient back), bnrc = recomputed (reduction only, finalize, the dgrad again
+        # with the BN backward applied). Dense 1x1 stride-1 layers reducing into >= 2x the channels only.
+        chain = (tuple(kern) == (1, 1) and tuple(stride) == (1, 1) and g == 1 and cp == c and 2 * k <= c and
+                 int(lib.rn_conv_tile(C.byref(d), 1)) >= 128)
+        if chain and ("bnst" in modes or "bnrc" in modes):
+            bd = L.BNDesc(dtype=L.RN_BF16, m=n * h * w, c=cp, c_real=c, eps=2e-5, momentum=0.9, fix_gamma=0, relu=1)
+            nrb = int(lib.rn_conv_bnred_blocks(C.byref(d)))
+            bws = torch.empty(int(lib.rn_bn_workspace_bytes(C.byref(bd))) // 4 + 16, device=dev)
+            g1, fan = torch.empty_like(x), torch.randn(x.numel(), device=dev).to(torch.bfloat16)
+            coef, dg, db = torch.empty(4 * cp, device=dev), torch.empty(cp, device=dev), torch.empty(cp, device=dev)
+
+            def stored():
+                r = lib.rn_conv_bwd_data_bnred(C.byref(d), P(yv), P(wc), P(g1), None, P(x), P(bnv), P(bnv), P(bnv), 1,
+                                               P(bnpart), st)
+                return r or lib.rn_bn_bwd_part(C.byref(bd), P(bnpart), nrb, P(x), P(g1), P(dx), P(fan), P(bnv), P(bnv),
+                                               P(bnv), P(bnv), P(bnv), P(dg), P(db), P(bws), st)
+
+            def recomputed():
+                r = lib.rn_conv_bwd_data_bnred(C.byref(d), P(yv), P(wc), None, None, P(x), P(bnv), P(bnv), P(bnv), 1,
+                                               P(bnpart), st)
+                r = r or lib.rn_bn_bwd_finalize(C.byref(bd), P(bnpart), nrb, P(bnv), P(bnv), P(bnv), P(dg), P(db),
+                                                P(coef), st)
+                return r or lib.rn_conv_bwd_data_bnapply(C.byref(d), P(yv), P(wc), P(dx), P(fan), P(x), P(coef),
+                                                         P(bnv), P(bnv), 1, st)
+            calls["bnst"], calls["bnrc"] = stored, recomputed
         flops = 2.0 * n * d.p * d.q * k * (c // g) * kern[0] * kern[1]
         # algorithmic HBM bytes (bf16): x + w + y (+ residual for fwd); per-mode roofline time
         xb, yb, wb = 2.0 * n * h * w * c, 2.0 * n * d.p * d.q * k, 2.0 * k * kern[0] * kern[1] * (c // g)
         algb = {"fwd": xb + wb + yb * (2 if res else 1), "dgrad": yb + wb + xb, "wgrad": xb + yb + 2 * wb,
-                "dgbn": yb + wb + 2 * xb}
+                "dgbn": yb + wb + 2 * xb, "bnst": yb + wb + 6 * xb, "bnrc": 2 * (yb + wb) + 4 * xb}
         row = "%-26s %3d %-22s %-5s" % (name[:26], cnt, "%dx%dx%d>%d k%d s%d" % (h, w, c, k, kern[0], stride[0]),
                                        "g%d" % g if g > 1 else ("+res" if res else ""))
         for m in modes:
+            if m not in calls:  # (bnst / bnrc on a layer without that chain)
+                row += "%23s" % "-"
+                continue
             fn = calls[m]
             for _ in range(3):
                 L.check(fn(), m)
