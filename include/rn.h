@@ -83,6 +83,11 @@ int32_t rn_conv_tile(const rn_conv_desc* d, int32_t mode);
  * k = 64 or 128 unpadded, c a multiple of 128, n h w c 2 bytes below 2^31 (rn_set_tuning 27 = 1: never).
  * 0 otherwise (the tiles). A caller takes the recomputed BatchNorm backward only there. */
 int32_t rn_conv_dgrad_streamed(const rn_conv_desc* d);
+/* 1 where rn_conv_fwd_x of `d` (bf16 output, no bias) with the input transform, the residual or the statistics
+ * runs the streaming forward kernel (the plain form too where c = 64): bf16, dense 1x1 stride 1 without padding, c = 64 or 128
+ * unpadded, k an unpadded multiple of 128, n h w max(k, c) 2 bytes below 2^31, 224-row statistics blocks
+ * (rn_set_tuning 29 = 1: never). 0 otherwise (the tiles). rn_conv_bn_part_rows is 224 either way. */
+int32_t rn_conv_fwd_streamed(const rn_conv_desc* d);
 /* Int8 forward of a quantized convolution (resnet_int8 / attach_quantize_node graphs: conv over
  * Quantization_int8(data) and Quantization_int8(weight), symbol/int8_api.py:120-151). x_codes /
  * w_codes are the int8 codes (value = code * unit; NHWC / KRSC, channel stride d->c bytes, a multiple
@@ -683,7 +688,13 @@ const char* rn_last_error(void);
  *      within 2^-21 |v / unit| of a half-integer -- the same codes bit for bit, fewer instructions),
  * 28 = 1 at rn_conv_desc_init time: depthwise 3x3 convolutions (groups = c = k) on the block-diagonal
  *      tiles (default 0: the depthwise kernels, d->grouped_direct = 2); 28 = n >= 2: those kernels on at
- *      most n workgroups (rounded up to a whole number of chunk periods; tests of the work-item loop). */
+ *      most n workgroups (rounded up to a whole number of chunk periods; tests of the work-item loop),
+ * 29 = 1: the 1x1 / stride-1 forward convolutions from C = 64 or 128 into K % 128 == 0 channels (the pre-activation
+ *      units' conv3, stage 1's shortcut) on the 224-row tiles (default 0: fwd1x1_stream_kernel, which streams their
+ *      rows with the weights in registers and the transform, residual and statistics per lane); 29 = 2: that
+ *      kernel with 32 channels per wave (default 64 where K % 256 == 0), for every eligible shape in every form;
+ *      29 = 3: every form at the default width (by default the C = 128 form without transform, residual and
+ *      statistics stays on its tile, which measured faster). */
 int rn_set_tuning(int32_t key, int32_t value);
 int32_t rn_version(void);
 /* Build id baked in at compile time: a hash of the sources (csrc/*.hip, csrc/*.h, include/rn.h) and the

@@ -4661,6 +4661,305 @@ int d1_stream_launch(const rn_conv_desc* d, int epi, const void* dy, const void*
   return rn_check_launch("dgrad1x1_stream");
 }
 
+// ---- The channel-expanding 1x1 / stride-1 forward convolutions (the pre-activation units' conv3 and stage-1's
+// shortcut, symbol/resnet.py:22-31: Cin = 64 / 128 into Kout = 4 Cin), streamed as dgrad1x1_stream_kernel streams
+// its mirror image: y[m][k] = sum_c act(x)[m][c] w[k][c] (the KRSC copy) has the same wave / lane mapping -- the
+// weights' fragments (rows permuted so that output lane (g, i) holds channels 8 g .. 8 g + 7 of row i) in
+// registers for the whole kernel, x from global memory straight into the MFMA B operand, 14 unrolled 16-row steps
+// with the next step's loads issued first, k-steps accumulated in the tile's order (y is bit-identical to
+// igemm_big_kernel's). On the 224x128 tile these layers' epilogue (statistics, residual, transform) ran serialised
+// behind the main loop; here it is per-lane work on accumulators that already hold whole 16-byte chunks.
+// XF: max(x sc + sh, 0) rounded to bf16 (as bn_apply_kernel and the tiles' XF) on the loaded B registers; a row
+// past a short block contributes zeros AFTER the transform, as the tiles' zero-filled chunks do. ADD: the residual.
+// STATS: igemm_big_kernel's EPI 1 partials of the stored values, part[block][S1 | S2 | pivot][K], one per 224-row
+// block; pivot = the block's first row's convolution value rounded to bf16, BEFORE the residual (as EPI 1 takes
+// it from the staged accumulators). All three are compile-time (see dgrad1x1_stream_kernel's ADD).
+struct F1Args {
+  const bf16_t* x;    // [M][C]
+  const bf16_t* w;    // [K][C] (the KRSC copy of a 1x1 conv)
+  bf16_t* y;          // [M][K]
+  const bf16_t* add;  // (ADD) [M][K]
+  const float *in_sc, *in_sh;  // (XF) [C]
+  float* part;        // (STATS) [M / 224][3][K]
+  int M, C, K, ncg;
+};
+template <int KS, int XF, int ADD, int STATS, int NH>
+__global__ __launch_bounds__(256, 2) void fwd1x1_stream_kernel(F1Args p) {
+  constexpr bool kLds = XF && KS == 4 && NH == 2;
+  __shared__ __attribute__((aligned(16))) float xtab[kLds ? 2 * 128 : 4];
+  // The epilogue's layout. The MFMAs leave lane (g, i) with row i's channels 8 g .. 8 g + 7 of each 32-channel
+  // half: a store of them as they lie puts 4 rows' 16-byte pieces into every 4 consecutive lanes, and stored that
+  // way the kernel was slower than the tile in its plain form (DESIGN.md 3 has the figures). So each step's
+  // accumulators go through the wave's own LDS rows (fp32, 16-byte slots XORed with the row: no bank conflicts; a
+  // wave's LDS accesses execute in order, so a wait for its own writes is enough, no barrier) and come back with
+  // lane l holding chunk l % CH of row l / CH (+ RI j): every residual load and output store covers whole lines,
+  // and a lane's 8 channels are the same in every step, so the statistics take 24 registers.
+  constexpr int CH = 4 * NH, RI = 64 / CH, SL = 8 * NH;  // chunks per row, rows per instruction, fp32 slots per row
+  __shared__ float4 stg[4 * 16 * SL];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int g = lane >> 4, i = lane & 15;
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
+  const int rb = lid / p.ncg, cg = lid - rb * p.ncg;
+  const int m0 = rb * 224, rows = min(224, p.M - m0);
+  const int kw = (cg * 4 + wid) * 32 * NH;  // this wave's 32 NH output channels
+  const int ec = lane % CH, er = lane / CH;  // (epilogue) this lane's chunk, its row of each instruction's RI
+  const int k8 = kw + 8 * ec;
+  float4* const sw = stg + wid * 16 * SL;
+  v8s wf[NH][2][KS];
+#pragma unroll
+  for (int h = 0; h < NH; ++h)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int ch = kw + 32 * h + 8 * (i >> 2) + 4 * b + (i & 3);
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+        wf[h][b][ks] = *reinterpret_cast<const v8s*>(p.w + (int64_t)ch * p.C + ks * 32 + 8 * g);
+    }
+  // (XF) scale / shift of the lane's 8 KS input channels, fixed for the kernel: in registers, or (C = 128 at 64
+  // channels per wave, where they would be 64 more) in LDS, as dgrad1x1_stream_kernel's apply form keeps its constants
+  float xs[XF && !kLds ? KS : 1][8], xh[XF && !kLds ? KS : 1][8];
+  if constexpr (kLds) {  // thread t < 128: channel t
+    if (tid < 128) {
+      xtab[tid] = p.in_sc[tid];
+      xtab[128 + tid] = p.in_sh[tid];
+    }
+    __syncthreads();
+  } else if constexpr (XF) {
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        xs[ks][e] = p.in_sc[ks * 32 + 8 * g + e];
+        xh[ks][e] = p.in_sh[ks * 32 + 8 * g + e];
+      }
+  }
+  // (STATS) the sums of rows 0 .. 111 and 112 .. 223 apart, as the 4-wave tile's two wave rows keep them: at 64
+  // channels per wave a lane then adds the rows its twin lane of that tile adds, in the same order, and the
+  // partials come out bit-identical to that tile's
+  float s1[8], s2[8], t1[8], t2[8], piv[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) s1[e] = s2[e] = t1[e] = t2[e] = piv[e] = 0.f;
+  const uint4 z4 = make_uint4(0, 0, 0, 0);
+  // buffer loads and stores, rows past the block through an offset past the buffer (dgrad1x1_stream_kernel)
+  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, (short)0, p.M * p.C * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)p.add, (short)0, p.M * p.K * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, (short)0, p.M * p.K * 2, 0x00020000);
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  auto ld = [&](__amdgpu_buffer_rsrc_t rs, uint32_t off) __attribute__((always_inline)) {
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
+    return make_uint4(v.x, v.y, v.z, v.w);
+  };
+  // byte offset of the lane's epilogue chunk of step st, instruction j (kOob: a row past the block)
+  auto eoff = [&](int st, int j) __attribute__((always_inline)) {
+    const int r = st * 16 + RI * j + er;
+    return r < rows ? ((uint32_t)(m0 + r) * p.K + k8) * 2u : kOob;
+  };
+  auto load = [&](int st, uint4 (&d)[KS], uint4 (&av)[NH]) __attribute__((always_inline)) {
+    const int r = st * 16 + i;
+    const bool ok = r < rows;
+    const uint32_t m = (uint32_t)(m0 + r);
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) d[ks] = ld(rs_x, ok ? (m * p.C + ks * 32 + 8 * g) * 2u : kOob);
+    if constexpr (ADD)
+#pragma unroll
+      for (int j = 0; j < NH; ++j) av[j] = ld(rs_a, eoff(st, j));
+  };
+  uint4 d0[KS], a0[NH];
+#pragma unroll
+  for (int j = 0; j < NH; ++j) a0[j] = z4;
+  load(0, d0, a0);
+  // fully unrolled and branch-free, so hipcc's wait counts stay exact (dgrad1x1_stream_kernel; two and three
+  // steps of loads in flight measured the same as one)
+#pragma unroll
+  for (int st = 0; st < 14; ++st) {
+    uint4 d1[KS], a1[NH];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) d1[ks] = z4;
+#pragma unroll
+    for (int j = 0; j < NH; ++j) a1[j] = z4;
+    if (st + 1 < 14) load(st + 1, d1, a1);  // (compile-time)
+    if (STATS && st == 7)  // (compile-time) row 112: the second half's sums start
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        t1[e] = s1[e]; t2[e] = s2[e];
+        s1[e] = s2[e] = 0.f;
+      }
+    if constexpr (XF) {
+      const bool ok = st * 16 + i < rows;
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        float f[8], ka[8], kb[8];
+        if constexpr (kLds) {
+          // through an offset hipcc cannot see through, or it keeps all 64 words in registers again
+          int lo = ks * 32 + 8 * g;
+          asm volatile("" : "+v"(lo));
+          *reinterpret_cast<float4*>(ka) = *reinterpret_cast<const float4*>(&xtab[lo]);
+          *reinterpret_cast<float4*>(ka + 4) = *reinterpret_cast<const float4*>(&xtab[lo + 4]);
+          *reinterpret_cast<float4*>(kb) = *reinterpret_cast<const float4*>(&xtab[128 + lo]);
+          *reinterpret_cast<float4*>(kb + 4) = *reinterpret_cast<const float4*>(&xtab[128 + lo + 4]);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            ka[e] = xs[ks][e];
+            kb[e] = xh[ks][e];
+          }
+        }
+        chunk_to_f(d0[ks], f, (const bf16_t*)nullptr);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = fmaxf(fmaf(f[e], ka[e], kb[e]), 0.f);
+        const uint4 o = f_to_chunk(f, (const bf16_t*)nullptr);
+        // (relu(0 sc + sh) is not zero; per word: a select of whole uint4s goes through the stack)
+        d0[ks] = make_uint4(ok ? o.x : 0u, ok ? o.y : 0u, ok ? o.z : 0u, ok ? o.w : 0u);
+      }
+    }
+    v4f acc[NH][2];
+#pragma unroll
+    for (int h = 0; h < NH; ++h)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) acc[h][b] = v4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int h = 0; h < NH; ++h)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+          acc[h][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[h][b][ks], __builtin_bit_cast(v8s, d0[ks]), acc[h][b],
+                                                              0, 0, 0);
+    // the MFMA results' read wait states, explicitly, once per step (dgrad1x1_stream_kernel)
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_nop 7\n\ts_nop 7");
+    __builtin_amdgcn_sched_barrier(0);
+    // row i's channels 32 h + 8 g + 4 b .. + 3 -> slot 2 (4 h + g) + b of LDS row i
+#pragma unroll
+    for (int h = 0; h < NH; ++h)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+        sw[i * SL + ((2 * (4 * h + g) + b) ^ (i & (SL - 1)))] =
+            make_float4(acc[h][b][0], acc[h][b][1], acc[h][b][2], acc[h][b][3]);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's staged rows have landed (as igemm_big_kernel's)
+#pragma unroll
+    for (int j = 0; j < NH; ++j) {
+      const int rr = RI * j + er;
+      float v[8];
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const float4 t = sw[rr * SL + ((2 * ec + b) ^ (rr & (SL - 1)))];
+        v[4 * b] = t.x; v[4 * b + 1] = t.y; v[4 * b + 2] = t.z; v[4 * b + 3] = t.w;
+      }
+      if (STATS && st == 0 && j == 0) {  // (compile-time) the pivots: row m0's rounded values, held by lanes er = 0
+        float pv[8];
+        chunk_to_f(f_to_chunk(v, (const bf16_t*)nullptr), pv, (const bf16_t*)nullptr);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) piv[e] = __shfl(pv[e], ec, 64);
+      }
+      if constexpr (ADD) {
+        float af[8];
+        chunk_to_f(a0[j], af, (const bf16_t*)nullptr);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += af[e];
+      }
+      const uint4 out = f_to_chunk(v, (const bf16_t*)nullptr);
+      if constexpr (STATS) {  // on the stored (rounded) values
+        const bool ok = st * 16 + rr < rows;
+        float gv[8];
+        chunk_to_f(out, gv, (const bf16_t*)nullptr);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float dv = ok ? gv[e] - piv[e] : 0.f;
+          s1[e] += dv;
+          s2[e] = fmaf(dv, dv, s2[e]);
+        }
+      }
+      __builtin_amdgcn_raw_buffer_store_b128(u32x4{out.x, out.y, out.z, out.w}, rs_y, eoff(st, j), 0, 0);
+    }
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) d0[ks] = d1[ks];
+#pragma unroll
+    for (int j = 0; j < NH; ++j) a0[j] = a1[j];
+  }
+  if constexpr (STATS) {  // the RI row lanes of each chunk: xor CH, 2 CH, ..; the lanes er = 0 store
+#pragma unroll
+    for (int o = CH; o < 64; o <<= 1)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        s1[e] += __shfl_xor(s1[e], o, 64);
+        s2[e] += __shfl_xor(s2[e], o, 64);
+        t1[e] += __shfl_xor(t1[e], o, 64);
+        t2[e] += __shfl_xor(t2[e], o, 64);
+      }
+    if (er == 0)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float* dst = p.part + (int64_t)rb * 3 * p.K + k8 + e;
+        dst[0] = t1[e] + s1[e];
+        dst[p.K] = t2[e] + s2[e];
+        dst[2 * p.K] = piv[e];
+      }
+  }
+}
+
+// fwd1x1_stream_kernel for this forward? rn_set_tuning 29: 0 = the shapes and epilogue forms that measured faster
+// than the 224-row tiles (profiles/fwd_stream), 1 = never, 2 = every eligible shape and form, 32 channels per wave
+// (tests), 3 = every eligible shape and form at the default width (tests, and the measurement behind the default's
+// one exclusion). (224-row BN partial blocks, as the tiles' with rn_set_tuning 9 = 0.)
+bool f1_stream_shape(const rn_conv_desc* d) {
+  // (keys 4 = 1 and 3 take the tiles' statistics off their 224-row blocks: rn_conv_bn_part_rows follows the tiles)
+  return g_tune[RN_TUNE_FWD_STREAM] != 1 && g_tune[RN_TUNE_IGEMM_ROWS] != 1 && g_tune[RN_TUNE_IGEMM_BIG] != 1 &&
+         !g_tune[RN_TUNE_DIAG_IGEMM_L1] && d->dtype == RN_BF16 && d->groups <= 1 &&
+         d->r == 1 && d->s == 1 && d->stride_h == 1 && d->stride_w == 1 && d->pad_h == 0 && d->pad_w == 0 &&
+         d->c == d->c_real && (d->c == 64 || d->c == 128) && d->k == d->k_pad && d->k % 128 == 0 &&
+         // (the buffer descriptors' byte counts are ints)
+         (int64_t)d->n * d->h * d->w * std::max(d->k, d->c) * 2 <= INT32_MAX;
+}
+bool f1_stream_ok(const rn_conv_desc* d, int32_t y_dtype, const float* bias, const float* in_scale, const float* part,
+                  const void* add_src) {
+  // (measured cold, profiles/fwd_stream/conv_bench_*.log and DESIGN.md 3: both classes faster than the tiles in
+  // every form the step calls and in the plain form with a residual, C = 64 in the plain form too; the plain
+  // C = 128 form without a residual alone was slower than its tile, conv_bench_plain_cold_*.log)
+  const bool plain = !in_scale && !part && !add_src;
+  return f1_stream_shape(d) && y_dtype == RN_BF16 && !bias && (g_tune[RN_TUNE_FWD_STREAM] >= 2 || d->c == 64 || !plain);
+}
+int f1_stream_launch(const rn_conv_desc* d, const void* x, const void* w, void* y, const void* add,
+                     const float* in_sc, const float* in_sh, float* part, hipStream_t st) {
+  F1Args a{};
+  a.x = (const bf16_t*)x; a.w = (const bf16_t*)w; a.y = (bf16_t*)y; a.add = (const bf16_t*)add;
+  a.in_sc = in_sc; a.in_sh = in_sh; a.part = part;
+  const int nh = (d->k % 256 == 0 && g_tune[RN_TUNE_FWD_STREAM] != 2) ? 2 : 1;
+  a.M = d->n * d->h * d->w; a.C = d->c; a.K = d->k; a.ncg = d->k / (128 * nh);
+  const dim3 grid((unsigned)(ceil_div(a.M, 224) * a.ncg));
+#define RN_F1N(KSV, XV, AV, SV)                                                                            \
+  if (nh == 2) hipLaunchKernelGGL((fwd1x1_stream_kernel<KSV, XV, AV, SV, 2>), grid, dim3(256), 0, st, a); \
+  else hipLaunchKernelGGL((fwd1x1_stream_kernel<KSV, XV, AV, SV, 1>), grid, dim3(256), 0, st, a);
+#define RN_F1S(KSV, XV, AV) \
+  if (part) {               \
+    RN_F1N(KSV, XV, AV, 1)  \
+  } else {                  \
+    RN_F1N(KSV, XV, AV, 0)  \
+  }
+#define RN_F1A(KSV, XV) \
+  if (add) {            \
+    RN_F1S(KSV, XV, 1)  \
+  } else {              \
+    RN_F1S(KSV, XV, 0)  \
+  }
+#define RN_F1(KSV)  \
+  if (in_sc) {      \
+    RN_F1A(KSV, 1)  \
+  } else {          \
+    RN_F1A(KSV, 0)  \
+  }
+  if (d->c == 64) {
+    RN_F1(2)
+  } else {
+    RN_F1(4)
+  }
+#undef RN_F1
+#undef RN_F1A
+#undef RN_F1S
+#undef RN_F1N
+  return rn_check_launch("fwd1x1_stream");
+}
+
 }  // namespace
 
 extern "C" {
@@ -4729,6 +5028,8 @@ int rn_conv_fwd_x(const rn_conv_desc* d, const void* x, const void* w, void* y, 
   }
   if (band_ok(d) && !add_src && !bias && !part && y_dtype == RN_BF16)
     return band_launch(d, x, w, y, 0, as_stream(stream), in_scale, in_shift);
+  if (f1_stream_ok(d, y_dtype, bias, in_scale, part, add_src))
+    return f1_stream_launch(d, x, w, y, add_src, in_scale, in_shift, part, as_stream(stream));
   IgemmArgs a = make_igemm_args(d, 0);
   a.x = x; a.w = w; a.y = y; a.add = add_src; a.bias = bias; a.stats = part;
   a.in_sc = in_scale; a.in_sh = in_shift;
@@ -4804,6 +5105,11 @@ int32_t rn_conv_tile(const rn_conv_desc* d, int32_t mode) {
 }
 
 int32_t rn_conv_dgrad_streamed(const rn_conv_desc* d) { return d && d1_stream_ok(d, nullptr) ? 1 : 0; }
+
+int32_t rn_conv_fwd_streamed(const rn_conv_desc* d) {  // (a fused form: the input transform set)
+  static const float xf = 0.f;
+  return d && f1_stream_ok(d, RN_BF16, nullptr, &xf, nullptr, nullptr) ? 1 : 0;
+}
 
 int32_t rn_conv_bn_part_rows(const rn_conv_desc* d, int32_t mode) {
   if (d && mode == 2) return rn_conv_tile(d, 2) == 64 ? 64 : 224;  // int8 forward: per wave row / tile

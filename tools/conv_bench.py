@@ -5,6 +5,9 @@ python tools/conv_bench.py [--graph resnet50|resnext50|resnet50_int8|mobilenet] 
 Prints one line per unique shape (count = occurrences per step) and the per-step totals.
 python tools/conv_bench.py --only dgbn,bnst,bnrc --cold --filter conv1: the BatchNorm backward chain behind each conv1
 data gradient, stored against recomputed (in the step these tensors are not cache-resident: time them cold).
+python tools/conv_bench.py --only fwdx --cold --filter stage1: the forward as the step calls it (rn_conv_fwd_x with the
+BatchNorm+ReLU input transform, the residual where the graph has one, the BatchNorm statistics of the output where a
+BatchNorm reads it -- marked +st).
 """
 import argparse
 import ctypes as C
@@ -20,9 +23,10 @@ def main():
     ap.add_argument("--graph", default="resnet50")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--only", default="fwd,dgrad,wgrad", help="modes among fwd, dgrad, wgrad, dgbn (dgrad + BN reduction), bnst / bnrc (the "
+    ap.add_argument("--only", default="fwd,dgrad,wgrad", help="modes among fwd, fwdx (fwd + input transform, statistics), dgrad, wgrad, dgbn (dgrad + BN reduction), bnst / bnrc (the "
                     "BN backward chain of a conv1 data gradient, stored / recomputed; run them with --cold)")
-    ap.add_argument("--filter", default="")
+    ap.add_argument("--filter", default="", help="layer-name substrings, comma-separated")
+    ap.add_argument("--tune", default="", help="rn_set_tuning pairs, key=value comma-separated (e.g. 29=1)")
     ap.add_argument("--cold", action="store_true", help="evict L2/MALL (write 512 MB) before every timed call")
     a = ap.parse_args()
     import torch
@@ -33,6 +37,9 @@ def main():
            "resnet50_int8": graphs.resnet50_int8, "mobilenet": graphs.mobilenet_1_0}[a.graph]()
     plan = Plan(sym, [("data", (a.batch, 3, 224, 224))], [("softmax_label", (a.batch,))])
     lib = L.load()
+    for kv in filter(None, a.tune.split(",")):
+        L.check(lib.rn_set_tuning(*map(int, kv.split("="))), "tune")
+    bn_in = {id(op.x) for op in plan.ops if op.kind == "bn"}  # tensors a BatchNorm reads: their producer emits statistics
     shapes = {}
     for op in plan.ops:
         if op.kind != "conv":
@@ -40,17 +47,18 @@ def main():
         x, y = op.x, op.y
         key = (x.n, x.h, x.w, x.cp, x.c, y.c, op.kernel, op.stride, op.pad, op.groups, op.res is not None)
         if key not in shapes:
-            shapes[key] = [op.name, 0]
+            shapes[key] = [op.name, 0, False]
         shapes[key][1] += 1
+        shapes[key][2] |= id(y) in bn_in
     dev = torch.device("cuda:0")
     flush = torch.empty(128 << 20, dtype=torch.float32, device=dev) if a.cold else None
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     modes = a.only.split(",")
     tot = {m: 0.0 for m in modes}
     flops_tot = 0.0
-    print("%-26s %3s %-22s %-5s" % ("layer", "n", "shape", "") + "".join("%23s" % m for m in modes))
-    for key, (name, cnt) in shapes.items():
-        if a.filter and a.filter not in name:
+    print("%-26s %3s %-22s %-7s" % ("layer", "n", "shape", "") + "".join("%23s" % m for m in modes))
+    for key, (name, cnt, stats) in shapes.items():
+        if a.filter and not any(f in name for f in a.filter.split(",")):
             continue
         n, h, w, cp, c, k, kern, stride, pad, g, res = key
         d = L.ConvDesc(dtype=L.RN_BF16, n=n, h=h, w=w, c=cp, c_real=c, k=k, k_pad=_pad8(k), r=kern[0], s=kern[1],
@@ -70,8 +78,12 @@ def main():
         bnv = torch.rand(cp, device=dev) * 0.5 + 0.5
         bnpart = torch.empty(int(lib.rn_conv_bnred_blocks(C.byref(d))) * cp * 2 + 16, device=dev)
         L.check(lib.rn_conv_weight_pack(C.byref(d), P(wm), P(wk), P(wc), st), "pack")
+        fpart = torch.empty(int(lib.rn_conv_bnstats_blocks(C.byref(d))) * 3 * d.k_pad + 16, device=dev)
+        xsc, xsh = torch.rand(cp, device=dev) * 0.5 + 0.5, torch.randn(cp, device=dev) * 0.5
         calls = {
             "fwd": lambda: lib.rn_conv_fwd(C.byref(d), P(x), P(wk), P(y), L.RN_BF16, P(yv) if res else None, None, st),
+            "fwdx": lambda: lib.rn_conv_fwd_x(C.byref(d), P(x), P(wk), P(y), L.RN_BF16, P(yv) if res else None, None,
+                                              P(xsc), P(xsh), P(fpart) if stats else None, st),
             "dgrad": lambda: lib.rn_conv_bwd_data(C.byref(d), P(yv), P(wc), P(dx), None, st),
             "wgrad": lambda: lib.rn_conv_bwd_filter_ws(C.byref(d), P(x), P(yv), P(dw), P(ws), ws_bytes, st),
             # the data gradient with the BatchNorm-backward reduction of its output in the epilogue (EPI 2,
@@ -79,6 +91,8 @@ def main():
             "dgbn": lambda: lib.rn_conv_bwd_data_bnred(C.byref(d), P(yv), P(wc), P(dx), None, P(x), P(bnv), P(bnv),
                                                        P(bnv), 1, P(bnpart), st),
         }
+        if g > 1 or cp != c or k % 8:  # (the input transform and the statistics: dense, unpadded layers)
+            calls.pop("fwdx")
         # the whole backward of the BatchNorm whose output gradient this data gradient is (the pre-activation
         # units' bn1 -> conv1), with the fan-in add of the step: bnst = stored (dgrad + reduction, then
         # rn_bn_bwd_part reads the gradient back), bnrc = recomputed (reduction only, finalize, the dgrad again
@@ -109,10 +123,11 @@ def main():
         flops = 2.0 * n * d.p * d.q * k * (c // g) * kern[0] * kern[1]
         # algorithmic HBM bytes (bf16): x + w + y (+ residual for fwd); per-mode roofline time
         xb, yb, wb = 2.0 * n * h * w * c, 2.0 * n * d.p * d.q * k, 2.0 * k * kern[0] * kern[1] * (c // g)
-        algb = {"fwd": xb + wb + yb * (2 if res else 1), "dgrad": yb + wb + xb, "wgrad": xb + yb + 2 * wb,
+        algb = {"fwd": xb + wb + yb * (2 if res else 1), "fwdx": xb + wb + yb * (2 if res else 1),
+                "dgrad": yb + wb + xb, "wgrad": xb + yb + 2 * wb,
                 "dgbn": yb + wb + 2 * xb, "bnst": yb + wb + 6 * xb, "bnrc": 2 * (yb + wb) + 4 * xb}
-        row = "%-26s %3d %-22s %-5s" % (name[:26], cnt, "%dx%dx%d>%d k%d s%d" % (h, w, c, k, kern[0], stride[0]),
-                                       "g%d" % g if g > 1 else ("+res" if res else ""))
+        row = "%-26s %3d %-22s %-7s" % (name[:26], cnt, "%dx%dx%d>%d k%d s%d" % (h, w, c, k, kern[0], stride[0]),
+                                       "g%d" % g if g > 1 else ("+res" if res else "") + ("+st" if stats and "fwdx" in modes else ""))
         for m in modes:
             if m not in calls:  # (bnst / bnrc on a layer without that chain)
                 row += "%23s" % "-"
