@@ -601,6 +601,27 @@ int rn_quant_int8_bwd(int32_t dtype, int64_t n, const void* x, const void* dy, v
                       rn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * PACT -- activation quantization with a learned clipping threshold: mx.sym.contrib.PACT and
+ * mx.sym.Custom(op_type="PACT_PY") (core/graph_optimize.py:183-187, core/operator/PACT.py:102-144).
+ * gamma: DEVICE pointer to the trainable threshold (fp32, shape (1,)), read by the kernels at run
+ * time. L = 2^nbits - 1, unit = gamma / L (one fp32 division).
+ * ------------------------------------------------------------------------------------- */
+/* Forward: c = x < gamma ? x : gamma (no lower clip), q = roundf(c / unit), value = q * unit rounded
+ * to dtype. out: the values (nullable only with codes). codes (nullable): int8 q, n a multiple of 16,
+ * nbits <= 7 (q <= 127; meant for non-negative x). unit (nullable): receives gamma / L.
+ * gamma <= 0: zeros. x / out / codes 16-byte aligned; any n without codes. */
+int rn_pact_fwd(int32_t dtype, int64_t n, const void* x, const float* gamma, int32_t nbits, void* out,
+                void* codes, float* unit, rn_stream_t stream);
+/* Workspace of rn_pact_bwd: one fp32 partial per block of a grid that depends on n only. */
+int64_t rn_pact_bwd_ws_bytes(int64_t n);
+/* Backward, one pass: dx = dy * [x < gamma] (+ add_src, nullable; the add in fp32, then rounded) and
+ * dgamma[0] = sum dy * [x >= gamma], WRITTEN (not accumulated) by a second small launch that adds the
+ * block partials in index order (32 consecutive partials per lane of one wave, then the 64 lane sums in
+ * lane order): no atomics, bit-identical from run to run. No gradient flows through unit. dx may alias dy or add_src. x / dy / dx / add_src 16-byte aligned; any n. */
+int rn_pact_bwd(int32_t dtype, int64_t n, const void* x, const void* dy, const float* gamma, void* dx,
+                const void* add_src, float* dgamma, void* ws, rn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Runtime.
  * ------------------------------------------------------------------------------------- */
 const char* rn_last_error(void);

@@ -556,6 +556,135 @@ __global__ void quant_bwd_kernel(int64_t n, const T* __restrict__ x, const T* __
   }
 }
 
+// ---- PACT (core/operator/PACT.py:102-144, PACT_PY): c = x < gamma ? x : gamma (no lower clip),
+// q = round(c / unit), value = q * unit with unit = gamma / (2^nbits - 1). gamma is read from device
+// memory by every launch (a trainable parameter: a captured graph replays with its current value).
+__device__ __forceinline__ float pact_code(float x, float g, float unit) {
+  const float c = x < g ? x : g;
+  return unit > 0.f ? roundf(c / unit) : 0.f;
+}
+// the values only: 16-byte chunks, then the tail (any n)
+template <typename T>
+__global__ __launch_bounds__(256) void pact_values_kernel(int64_t n, const T* __restrict__ x, T* __restrict__ out,
+                                                          const float* __restrict__ gamma, float levels,
+                                                          float* __restrict__ unit_out) {
+  const float g = *gamma;
+  const float unit = g / levels;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && unit_out) *unit_out = unit;
+  constexpr int CE = 16 / sizeof(T);
+  const int64_t nc = n / CE;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nc; i += (int64_t)gridDim.x * blockDim.x) {
+    float f[CE];
+    chunk_to_f(reinterpret_cast<const uint4*>(x)[i], f, (const T*)nullptr);
+#pragma unroll
+    for (int e = 0; e < CE; ++e) f[e] = pact_code(f[e], g, unit) * unit;
+    reinterpret_cast<uint4*>(out)[i] = f_to_chunk(f, (const T*)nullptr);
+  }
+  for (int64_t i = nc * CE + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = from_f<T>(pact_code(to_f(x[i]), g, unit) * unit);
+}
+// the values (out nullable) AND their int8 codes, 16 elements (one 16-byte code chunk) per thread as
+// quant_codes_kernel; the codes are 0 .. 2^nbits - 1 <= 127 for non-negative x (nbits <= 7)
+template <typename T>
+__global__ __launch_bounds__(256) void pact_codes_kernel(int64_t nchunk, const T* __restrict__ x, T* __restrict__ out,
+                                                         int8_t* __restrict__ codes, const float* __restrict__ gamma,
+                                                         float levels, float* __restrict__ unit_out) {
+  const float g = *gamma;
+  const float unit = g / levels;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && unit_out) *unit_out = unit;
+  constexpr int CE = 16 / sizeof(T);
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nchunk; i += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t cw[4];
+#pragma unroll
+    for (int h = 0; h < 16 / CE; ++h) {
+      float f[CE];
+      chunk_to_f(reinterpret_cast<const uint4*>(x)[i * (16 / CE) + h], f, (const T*)nullptr);
+#pragma unroll
+      for (int e = 0; e < CE; ++e) {
+        const float q = pact_code(f[e], g, unit);
+        f[e] = q * unit;
+        const int j = h * CE + e;
+        const uint32_t b = (uint32_t)(uint8_t)(int8_t)(int)q;
+        if ((j & 3) == 0) cw[j >> 2] = b;
+        else cw[j >> 2] |= b << (8 * (j & 3));
+      }
+      if (out) reinterpret_cast<uint4*>(out)[i * (16 / CE) + h] = f_to_chunk(f, (const T*)nullptr);
+    }
+    reinterpret_cast<uint4*>(codes)[i] = make_uint4(cw[0], cw[1], cw[2], cw[3]);
+  }
+}
+// backward: dx = dy * [x < gamma] (+ add, in fp32, then rounded), and the block's share of
+// dgamma = sum dy * [x >= gamma]: fp32 per-thread sums in element order, the wave butterfly, the four
+// waves through LDS, one partial per block -- no atomics, so the sum's order is fixed by the launch
+// geometry alone. dx may alias dy or add (each thread reads its elements before it writes them).
+constexpr int kPactBwdMaxBlocks = 2048;
+static inline int pact_bwd_blocks(int64_t n) {  // a function of n only (rn_pact_bwd_ws_bytes)
+  return (int)std::min<int64_t>(std::max<int64_t>((n + 2047) / 2048, 1), kPactBwdMaxBlocks);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void pact_bwd_kernel(int64_t n, const T* __restrict__ x, const T* dy, T* dx,
+                                                       const float* __restrict__ gamma, const T* add,
+                                                       float* __restrict__ part) {
+  const float g = *gamma;
+  constexpr int CE = 16 / sizeof(T);
+  const int64_t nc = n / CE;  // 16-byte chunks, then the tail
+  float s = 0.f;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nc; i += (int64_t)gridDim.x * blockDim.x) {
+    float fx[CE], fd[CE], fa[CE];
+    chunk_to_f(reinterpret_cast<const uint4*>(x)[i], fx, (const T*)nullptr);
+    chunk_to_f(reinterpret_cast<const uint4*>(dy)[i], fd, (const T*)nullptr);
+    if (add) chunk_to_f(reinterpret_cast<const uint4*>(add)[i], fa, (const T*)nullptr);
+#pragma unroll
+    for (int e = 0; e < CE; ++e) {
+      const bool pass = fx[e] < g;
+      s += pass ? 0.f : fd[e];
+      const float v = pass ? fd[e] : 0.f;
+      fd[e] = add ? v + fa[e] : v;
+    }
+    reinterpret_cast<uint4*>(dx)[i] = f_to_chunk(fd, (const T*)nullptr);
+  }
+  for (int64_t i = nc * CE + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const bool pass = to_f(x[i]) < g;
+    const float d = to_f(dy[i]);
+    s += pass ? 0.f : d;
+    float v = pass ? d : 0.f;
+    if (add) v += to_f(add[i]);
+    dx[i] = from_f<T>(v);
+  }
+  s = wave_sum(s);
+  __shared__ float ws[4];
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+}
+// the block partials (at most kPactBwdMaxBlocks = 64 * 32) added in index order, in two levels with a fixed shape:
+// lane l of one wave adds partials 32 l .. 32 l + 31 one after the other (all 32 loads in flight at once: a single
+// thread walking 2048 partials measured 95 us, each load waiting for the one before), then lane 0 adds the 64 lane
+// sums in lane order. dgamma[0] is written, not accumulated
+__global__ __launch_bounds__(64) void pact_dgamma_kernel(const float* __restrict__ part, int nblk,
+                                                         float* __restrict__ dgamma) {
+  static_assert(kPactBwdMaxBlocks == 64 * 32, "one wave, 32 partials per lane");
+  const int lane = threadIdx.x;
+  float v[32];
+#pragma unroll
+  for (int j = 0; j < 32; ++j) {
+    const int i = lane * 32 + j;
+    v[j] = i < nblk ? part[i] : 0.f;
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < 32; ++j) s += v[j];
+  __shared__ float ls[64];
+  ls[lane] = s;
+  __syncthreads();
+  if (lane == 0) {
+    float t = 0.f;
+#pragma unroll
+    for (int l = 0; l < 64; ++l) t += ls[l];
+    *dgamma = t;
+  }
+}
+
 // ---- Quantization_int8 of a BatchNorm(+ReLU) output, the BatchNorm applied on load
 // (rn_quant_int8_fwd_codes_bn). Thread = one 16-channel group (one 16-byte code chunk) of the rows
 // r0 + tr, r0 + tr + rl, ...; y = [relu](fmaf(x, scale, shift)) rounded to T exactly as bn_apply_kernel
@@ -1480,6 +1609,57 @@ int rn_quant_int8_bwd(int32_t dtype, int64_t n, const void* x, const void* dy, v
     hipLaunchKernelGGL(quant_bwd_kernel<float>, dim3(grid1d(n)), dim3(256), 0, st, n, (const float*)x,
                        (const float*)dy, (float*)dx, minmax, is_weight, (const float*)add_src);
   return rn_check_launch("quant_int8_bwd");
+}
+
+int rn_pact_fwd(int32_t dtype, int64_t n, const void* x, const float* gamma, int32_t nbits, void* out, void* codes,
+                float* unit, rn_stream_t stream) {
+  RN_CHECK_ARG(x && gamma && n > 0 && (out || codes), "bad arguments");
+  RN_CHECK_ARG(dtype == RN_BF16 || dtype == RN_F32, "bad dtype");
+  RN_CHECK_ARG(nbits >= 1 && nbits <= 16, "bad nbits");
+  RN_CHECK_ARG(!codes || nbits <= 7, "int8 codes need nbits <= 7 (codes up to 2^nbits - 1 must fit a signed byte)");
+  RN_CHECK_ARG(!codes || n % 16 == 0, "int8 codes: n must be a multiple of 16");
+  RN_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)codes & 15) == 0,
+               "16-byte aligned x / out / codes");
+  hipStream_t st = as_stream(stream);
+  const float levels = (float)((1 << nbits) - 1);
+  if (codes) {
+    const int64_t nc = n / 16;
+    if (dtype == RN_BF16)
+      hipLaunchKernelGGL(pact_codes_kernel<bf16_t>, dim3(grid1d(nc)), dim3(256), 0, st, nc, (const bf16_t*)x,
+                         (bf16_t*)out, (int8_t*)codes, gamma, levels, unit);
+    else
+      hipLaunchKernelGGL(pact_codes_kernel<float>, dim3(grid1d(nc)), dim3(256), 0, st, nc, (const float*)x,
+                         (float*)out, (int8_t*)codes, gamma, levels, unit);
+  } else {
+    const int64_t nc = n / (dtype == RN_BF16 ? 8 : 4) + 1;
+    if (dtype == RN_BF16)
+      hipLaunchKernelGGL(pact_values_kernel<bf16_t>, dim3(grid1d(nc)), dim3(256), 0, st, n, (const bf16_t*)x,
+                         (bf16_t*)out, gamma, levels, unit);
+    else
+      hipLaunchKernelGGL(pact_values_kernel<float>, dim3(grid1d(nc)), dim3(256), 0, st, n, (const float*)x,
+                         (float*)out, gamma, levels, unit);
+  }
+  return rn_check_launch("pact_fwd");
+}
+
+int64_t rn_pact_bwd_ws_bytes(int64_t n) { return n > 0 ? (int64_t)sizeof(float) * pact_bwd_blocks(n) : 0; }
+
+int rn_pact_bwd(int32_t dtype, int64_t n, const void* x, const void* dy, const float* gamma, void* dx,
+                const void* add_src, float* dgamma, void* ws, rn_stream_t stream) {
+  RN_CHECK_ARG(x && dy && gamma && dx && dgamma && ws && n > 0, "bad arguments");
+  RN_CHECK_ARG(dtype == RN_BF16 || dtype == RN_F32, "bad dtype");
+  RN_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)dx & 15) == 0 &&
+                   ((uintptr_t)add_src & 15) == 0, "16-byte aligned x / dy / dx / add_src");
+  hipStream_t st = as_stream(stream);
+  const int nblk = pact_bwd_blocks(n);
+  if (dtype == RN_BF16)
+    hipLaunchKernelGGL(pact_bwd_kernel<bf16_t>, dim3(nblk), dim3(256), 0, st, n, (const bf16_t*)x, (const bf16_t*)dy,
+                       (bf16_t*)dx, gamma, (const bf16_t*)add_src, (float*)ws);
+  else
+    hipLaunchKernelGGL(pact_bwd_kernel<float>, dim3(nblk), dim3(256), 0, st, n, (const float*)x, (const float*)dy,
+                       (float*)dx, gamma, (const float*)add_src, (float*)ws);
+  hipLaunchKernelGGL(pact_dgamma_kernel, dim3(1), dim3(64), 0, st, (const float*)ws, nblk, dgamma);
+  return rn_check_launch("pact_bwd");
 }
 
 }  // extern "C"

@@ -19,6 +19,28 @@ class InitDesc(str):
         return ret
 
 
+def _init_from_attr(desc, arr):
+    """A variable's own initializer -- its `__init__` attribute, the JSON `[name, kwargs]` that
+    `init=mx.init.Constant(8.0)` dumps or the reference writes by hand (core/graph_optimize.py:32-34) --
+    overrides the global one, as in MXNet's Initializer.__call__: the named initializer's _init_weight
+    fills the array whatever the variable's suffix. Returns whether the attribute was there."""
+    init = (getattr(desc, "attrs", None) or {}).get("__init__")
+    if not init:
+        return False
+    klass, kwargs = json.loads(init)
+    create(klass, **kwargs)._init_weight(desc, arr)
+    return True
+
+
+def create(name, **kwargs):
+    """The initializer registered under `name` (mx.init.create / mx.init.register's lower-case names)."""
+    try:
+        cls = _REGISTRY[str(name).lower()]
+    except KeyError:
+        raise ValueError("Unknown initializer %s (known: %s)" % (name, sorted(_REGISTRY)))
+    return cls(**kwargs)
+
+
 class Initializer:
     def __init__(self, **kwargs):
         self._kwargs = kwargs
@@ -27,6 +49,8 @@ class Initializer:
         return json.dumps([self.__class__.__name__.lower(), self._kwargs])
 
     def __call__(self, desc, arr):
+        if _init_from_attr(desc, arr):
+            return
         name = str(desc)
         if name.endswith("_weight"):
             self._init_weight(name, arr)
@@ -69,19 +93,23 @@ class Constant(Initializer):
         self.value = value
 
     def __call__(self, desc, arr):
-        arr[:] = self.value
+        if not _init_from_attr(desc, arr):
+            arr[:] = self.value
 
-    _init_weight = __call__
+    def _init_weight(self, name, arr):
+        arr[:] = self.value
 
 
 class Zero(Constant):
     def __init__(self):
         super().__init__(0.0)
+        self._kwargs = {}
 
 
 class One(Constant):
     def __init__(self):
         super().__init__(1.0)
+        self._kwargs = {}
 
 
 class Normal(Initializer):
@@ -105,3 +133,7 @@ class Uniform(Initializer):
 class MSRAPrelu(Xavier):
     def __init__(self, factor_type="avg", slope=0.25):
         super().__init__("gaussian", factor_type, 2.0 / (1 + slope ** 2))
+
+
+_REGISTRY = {"constant": Constant, "zero": Zero, "zeros": Zero, "one": One, "ones": One, "xavier": Xavier,
+             "normal": Normal, "uniform": Uniform, "msraprelu": MSRAPrelu}

@@ -198,6 +198,7 @@ class Module:
         initializer = initializer if initializer is not None else Uniform(0.01)
         ex = self._exec
         plan = ex.plan
+        var_attrs = self._symbol.attr_dict()  # a variable's own `__init__` wins over the global initializer
         for name in plan.param_names:
             shp = ex.param_shape[name]
             if arg_params is not None and name in arg_params:
@@ -207,7 +208,7 @@ class Module:
                 if arg_params is not None and not allow_missing:
                     raise MXNetError("%s is not presented" % name)
                 arr = nd.zeros(shp)
-                initializer(InitDesc(name), arr)
+                initializer(InitDesc(name, var_attrs.get(name)), arr)
                 v = arr.asnumpy()
             ex.set_param(name, v)
         for name in plan.aux_names:
@@ -219,7 +220,7 @@ class Module:
                 if aux_params is not None and not allow_missing:
                     raise MXNetError("%s is not presented" % name)
                 arr = nd.zeros(shp)
-                initializer(InitDesc(name), arr)
+                initializer(InitDesc(name, var_attrs.get(name)), arr)
                 v = arr.asnumpy()
             ex.set_aux(name, v)
         d = _dist()

@@ -357,6 +357,7 @@ def make_module_class(Module):
             shapes = dict(zip(self._symbol.list_arguments(), args))
             ashapes = dict(zip(self._symbol.list_auxiliary_states(), auxs))
             known = self._known()
+            var_attrs = self._symbol.attr_dict()  # a variable's own `__init__` wins over the global initializer
 
             def fill(names, given, shape_of):
                 out = {}
@@ -368,7 +369,7 @@ def make_module_class(Module):
                         if given is not None and not allow_missing:
                             raise MXNetError("%s is not presented" % name)
                         arr = nd.zeros(shape_of[name])
-                        initializer(InitDesc(name), arr)
+                        initializer(InitDesc(name, var_attrs.get(name)), arr)
                         out[name] = arr.asnumpy()
                 return out
             arg = fill([a for a in self._symbol.list_arguments() if a not in known], arg_params, shapes)

@@ -112,7 +112,32 @@ _reg(OpSpec("_contrib_Quantization_int8", ["data"], lambda n: ["minmax"], hint="
 # the fork's per-channel scale (data * scaler, scaler (1,C,1,1)): what merge_bn folds a BatchNorm into
 # (core/graph_optimize.py:90-93)
 _reg(OpSpec("_contrib_BroadcastScale", ["data", "scaler"], hint="broadcastscale"))
-_reg(OpSpec("Custom", lambda n: ["data"], hint="custom"))
+# the fork's PACT: activation quantization with a learned clipping threshold gamma (1,)
+# (core/graph_optimize.py:184-187)
+_reg(OpSpec("_contrib_PACT", ["data", "gamma"], hint="pact"))
+
+
+def _custom_prop(node):
+    """The CustomOpProp registered under the node's op_type (mx.operator.register), built as MXNet builds
+    it -- with the node's other attributes as strings -- or None for an unregistered op_type."""
+    from . import operator as _operator
+    cls = _operator.get_registry().get(str(node.attrs.get("op_type")))
+    if cls is None:
+        return None
+    return cls(**{k: str(v) for k, v in node.attrs.items() if k != "op_type" and not k.startswith("__")})
+
+
+def _custom_args(node):
+    prop = _custom_prop(node)
+    return ["data"] if prop is None else list(prop.list_arguments())
+
+
+def _custom_aux(node):
+    prop = _custom_prop(node)
+    return [] if prop is None else list(prop.list_auxiliary_states())
+
+
+_reg(OpSpec("Custom", _custom_args, _custom_aux, hint="custom"))
 
 
 def _variadic(opname, hint):
@@ -378,6 +403,19 @@ def _infer_node(n, shapes, partial):
             if i < len(ins):
                 _set(shapes, ins[i], (c,))
         _set(shapes, (n, 0), dshape)
+    elif op == "_contrib_PACT":
+        _set(shapes, ins[1], (1,))
+        _set(shapes, (n, 0), dshape)
+    elif op == "Custom" and _custom_prop(n) is not None:
+        # the registered prop's infer_shape: ([input shapes], [output shapes], [aux shapes]); an input
+        # whose shape is not known yet is passed empty, as MXNet passes it
+        prop = _custom_prop(n)
+        res = prop.infer_shape([list(_shape(shapes, i) or ()) for i in ins[:len(prop.list_arguments())]])
+        in_shapes, out_shapes = res[0], res[1]
+        aux_shapes = res[2] if len(res) > 2 else []
+        for i, shp in zip(ins, list(in_shapes) + list(aux_shapes)):
+            _set(shapes, i, shp)
+        _set(shapes, (n, 0), out_shapes[0])
     elif op in ("Activation", "identity", "Cast", "_contrib_Quantization_int8", "Custom"):
         if op == "_contrib_Quantization_int8" and len(ins) > 1:
             perch = _parse(n.attrs.get("is_weight_perchannel", False)) and _parse(n.attrs.get("is_weight", False))
@@ -548,6 +586,7 @@ def Group(symbols):
 class _Contrib:
     Quantization_int8 = staticmethod(_make("_contrib_Quantization_int8"))
     BroadcastScale = staticmethod(_make("_contrib_BroadcastScale"))
+    PACT = staticmethod(_make("_contrib_PACT"))
 
     def __getattr__(self, item):
         raise MXNetError("contrib operator %s is not provided by this runtime" % item)

@@ -6,7 +6,8 @@ gpu_list=[] meaning no GPU). A Module bound to mx.cpu() contexts runs here: ever
 (rn/executor.py) as a torch-CPU fp32 operator (oneDNN, the analogue of MXNet's MKL-DNN CPU path),
 with MXNet's semantics -- BatchNorm batch statistics with biased variance and momentum moving stats,
 fix_gamma / use_global_stats, SoftmaxOutput's p - onehot gradient, Quantization_int8 with EMA
-thresholds and the clipped STE, MXNet momentum SGD with wd_mult 0 on biases / betas -- and the same
+thresholds and the clipped STE, PACT with its learned threshold, MXNet momentum SGD with wd_mult 0 on
+biases / betas -- and the same
 flat fp32 parameter / gradient / momentum / aux buffers the GPU executor has, so Module,
 kvstore (gloo all-reduce over the flat gradient), checkpoints and metrics work unchanged.
 
@@ -44,6 +45,10 @@ class CPUExecutor:
         self._data = torch.zeros(plan.data_tensor.shape, dtype=torch.float32)
         self._label = None
         self._q = _QuantState()
+        # the last forward's discrete decisions, kept for parity tests that replay them in a higher precision (on
+        # the GPU they sit in device buffers): ReLU masks by Activation name, fake-quantized weights by quantizer
+        # name, PACT codes / x < gamma masks / units by gamma name
+        self.decisions = {"relu": {}, "wq": {}, "pact": {}}
         self._out = {}
         self._head = None
         self.num_update = 0
@@ -204,6 +209,8 @@ class CPUExecutor:
                 env[id(op.y)] = F.relu(get(op.x))
             elif k == "quant":
                 env[id(op.y)] = self._quant_act(get(op.x), op.q, train)
+            elif k == "pact":
+                env[id(op.y)] = self._pact(op.gamma, get(op.x), P(op.gamma), op.nbits)
             elif k == "add":
                 y = get(op.a) + get(op.b)
                 env[id(op.y)] = F.relu(y) if op.relu else y
@@ -235,6 +242,8 @@ class CPUExecutor:
                                                     float((top == lab[:, None]).any(1).sum()), 0.0])
             else:
                 raise RuntimeError("CPU executor: op kind %s" % k)
+            if getattr(op, "relu_name", None):
+                self.decisions["relu"][op.relu_name] = env[id(op.y)].detach() > 0
         self._out = {id(t): env[id(t)] for t in self.plan.outputs}
 
     def _bn(self, x, gamma, beta, mean_name, var_name, eps, momentum, fix_gamma, use_global, train):
@@ -276,6 +285,24 @@ class CPUExecutor:
             mask = ((x.detach() > -t) & (x.detach() < t)).to(x.dtype)
         return x * mask + (v - x.detach() * mask)
 
+    def _pact(self, name, x, g, nbits):
+        """PACT (core/operator/PACT.py:102-144): c = where(x < gamma, x, gamma) -- no lower clip --, rounded half
+        away from zero to the grid unit = gamma / (2^nbits - 1). Autograd sees only the where: dx = dy * [x < gamma],
+        dgamma = sum dy * [x >= gamma]; the unit is a constant of the backward, as in the reference. The last
+        forward's codes, mask and unit stay in self.decisions["pact"][name]."""
+        unit = (g / float(2 ** nbits - 1)).detach()
+        c = torch.where(x < g, x, g.expand_as(x))
+        with torch.no_grad():
+            if float(unit) > 0:
+                a = c / unit
+                t = torch.trunc(a)  # (a - t is exact: roundf, without floor(|a| + 0.5)'s double rounding)
+                q = t + torch.sign(a) * ((a - t).abs() >= 0.5).to(a.dtype)
+            else:
+                q = torch.zeros_like(c)
+            v = q * unit
+            self.decisions["pact"][name] = {"codes": q, "mask": x.detach() < g.detach(), "unit": float(unit)}
+        return v + (c - c.detach())  # (exactly v; the gradient is the where's)
+
     def _weight(self, w, qw, train):
         """Quantization_int8 on a weight (per tensor, no clip, plain STE: symbol/quant_ops.py:17-31)."""
         if qw is None:
@@ -284,4 +311,5 @@ class CPUExecutor:
         unit = t / float(2 ** (qw["nbits"] - 1) - 1)
         with torch.no_grad():
             v = _mx_round(w.detach() / unit) * unit if unit > 0 else torch.zeros_like(w)
+            self.decisions["wq"][qw["name"]] = v
         return w + (v - w.detach())

@@ -264,6 +264,9 @@ class Plan:
                     y = self._new_tensor(n, x.shape)
                     self.ops.append(PlanOp("quant", n.name, x=x, y=y, q=q))
                 done.add(id(n))
+            elif op == "_contrib_PACT" or op == "Custom":
+                self._lower_pact(n)
+                done.add(id(n))
             elif op == "Activation":
                 act = _parse(n.attrs.get("act_type"))
                 if act != "relu":
@@ -308,22 +311,65 @@ class Plan:
         self._fuse_bn_apply()
         self._mark_int8()
 
+    def _lower_pact(self, n):
+        """PACT (core/graph_optimize.py:180-187): mx.sym.contrib.PACT or mx.sym.Custom(op_type="PACT_PY"), the
+        activation quantizer with a learned clipping threshold -- out = round(min(x, gamma) / unit) * unit,
+        unit = gamma / (2^nbits - 1) (core/operator/PACT.py:102-144). gamma is an ordinary trainable parameter of
+        shape (1,): it joins the flat parameter / gradient / momentum buffers like a BatchNorm's. The Python
+        forward / backward of the CustomOp are never run; any other Custom op_type has no kernel here."""
+        if n.op == "Custom" and _parse(n.attrs.get("op_type")) != "PACT_PY":
+            raise PlanError("operator Custom (%s, op_type=%s) is not supported by the MI355X runtime"
+                            % (n.name, n.attrs.get("op_type")))
+        if len(n.inputs) != 2:
+            raise PlanError("%s: PACT takes data and gamma" % n.name)
+        g = n.inputs[1][0]
+        if g.op != "null" or g.name in self.input_shapes:
+            raise PlanError("%s: PACT's gamma must be a parameter Variable" % n.name)
+        if any(o.kind == "pact" and o.gamma == g.name for o in self.ops):
+            raise PlanError("%s: gamma %s is shared with another PACT node (not supported)" % (n.name, g.name))
+        nbits = int(_parse(n.attrs.get("nbits", 8)))
+        if not 1 <= nbits <= 16:
+            raise PlanError("%s: PACT nbits %d not supported" % (n.name, nbits))
+        x = self.tensor(n.inputs[0][0])
+        if x.kind != "act":
+            raise PlanError("%s: PACT of a non-activation tensor" % n.name)
+        y = self._new_tensor(n, x.shape)
+        self.ops.append(PlanOp("pact", n.name, x=x, y=y, gamma=g.name, nbits=nbits))
+
+    def _nonneg(self, t):
+        """Is activation tensor `t` known to be >= 0: written by a BatchNorm with fused ReLU, a relu op, an add
+        with ReLU, or a pooling of one of those (PACT has no lower clip: only then are its codes 0 .. 2^nbits - 1)?"""
+        for op in self.ops:
+            if op.y is t:
+                if op.kind in ("bn", "add"):
+                    return bool(op.relu)
+                return op.kind == "relu" or (op.kind == "pool" and self._nonneg(op.x))
+        return False
+
     def _mark_int8(self):
         """Quantized convolutions (a Quantization_int8 on both the data and the weight: resnet_int8,
         attach_quantize_node) whose input quantizer can also emit int8 codes run their forward on the
         int8 MFMAs (rn_conv_fwd_i8): exact integer sums of the codes, scaled by the two units, instead
-        of bf16 / fp32 products of the fake-quantized values. RN_INT8_MFMA=0: the fake-quant path."""
-        producer = {id(op.y): op for op in self.ops if op.kind == "quant"}
+        of bf16 / fp32 products of the fake-quantized values. RN_INT8_MFMA=0: the fake-quant path.
+        A PACT input quantizer qualifies with nbits <= 7 (its codes reach 2^nbits - 1) over a tensor known to be
+        non-negative (_nonneg); otherwise its convolution multiplies the fake-quantized values."""
+        producer = {id(op.y): op for op in self.ops if op.kind in ("quant", "pact")}
         on = os.environ.get("RN_INT8_MFMA", "1") != "0"
         for op in self.ops:
-            if op.kind == "quant":
+            if op.kind in ("quant", "pact"):
                 op.emit_codes = False
+            if op.kind == "pact":
+                op.codes_wgrad = False  # (never for PACT: the values are always written)
         for op in self.ops:
             if op.kind != "conv":
                 continue
             q = producer.get(id(op.x))
-            op.int8 = bool(on and op.qweight is not None and q is not None and op.groups == 1 and
-                           op.x.cp % 16 == 0 and q.q["nbits"] <= 8 and op.qweight["nbits"] <= 8 and
+            if q is not None and q.kind == "pact":
+                q_ok = q.nbits <= 7 and self._nonneg(q.x)
+            else:
+                q_ok = q is not None and q.q["nbits"] <= 8
+            op.int8 = bool(on and op.qweight is not None and q_ok and op.groups == 1 and
+                           op.x.cp % 16 == 0 and op.qweight["nbits"] <= 8 and
                            getattr(op, "xf", None) is None)
             op.qsrc = q if op.int8 else None
             if op.int8:
@@ -1226,6 +1272,17 @@ class Executor:
                         lst.append(self._call("rn_quant_int8_fwd", self.dtype, op.x.numel, self._p(self.act(op.x)),
                                               self._p(self.act(op.y)), self._ap(q["minmax"]), 0, tr, q["ema"],
                                               self._qfirst, q["nbits"], qwsp, sp))
+            elif op.kind == "pact":
+                # the same in training and inference; gamma is read on the device from the flat master buffer, so
+                # every step (and a replayed graph) sees the value the last update left. The values are always
+                # written; with emit_codes also the int8 codes and the unit the consumers' int8 forward reads
+                op.unit = self._zeros(1, self.torch.float32)
+                op.codes = self.torch.zeros(op.x.numel, dtype=self.torch.int8, device=self.device) \
+                    if op.emit_codes else None
+                c = self._call("rn_pact_fwd", self.dtype, op.x.numel, self._p(self.act(op.x)), self._pp(op.gamma),
+                               op.nbits, self._p(self.act(op.y)), self._p(op.codes), self._p(op.unit), sp)
+                F.append(c)
+                I.append(c)
             elif op.kind == "add" and getattr(op, "bn_a", None) is not None:
                 bna, bnb = op.bn_a, op.bn_b
                 other = op.b if op.bn_a_key == "a" else op.a
@@ -1529,6 +1586,7 @@ class Executor:
         wsp = self._p(self.ws)
         self.param_done_at = {}  # param -> index in self._bwd after which its grad is final
         self._gw = {}  # id(tensor) -> last writer of its gradient buffer: ("dgrad", call index, conv op)
+        self._pact_ws = None  # rn_pact_bwd's block partials: one buffer for every PACT (compute stream, plan order)
         # default on where the dgrad runs the 256-row tile (see RN_BN_EPILOGUE_STATS; =2: every dgrad)
         for op in plan.ops:
             if op.kind == "bn":
@@ -1819,6 +1877,23 @@ class Executor:
                     self._bwd.append(self._call("rn_quant_int8_bwd", self.dtype, op.x.numel, self._p(self.act(op.x)),
                                                 self._p(dy), self._p(out), self._ap(op.q["minmax"]), 0, self._p(add),
                                                 sp))
+            elif op.kind == "pact":
+                # dx = dy * [x < gamma] and dgamma = sum dy * [x >= gamma] in one pass (+ the ordered sum of its
+                # block partials, which writes the gradient). This call is the last writer of x's gradient and
+                # fuses no BatchNorm reduction: the BatchNorm that produced x runs its own rn_bn_bwd
+                if self._pact_ws is None:
+                    nmax = max(o.x.numel for o in plan.ops if o.kind == "pact")
+                    self._pact_ws = self._zeros(int(self.lib.rn_pact_bwd_ws_bytes(nmax)) // 4, self.torch.float32)
+                if op.x.needs_grad:
+                    out, add = gs.contribute(op.x)
+                    self._gw[id(op.x)] = ("other",)
+                else:  # (no consumer of dx: a scratch buffer takes it)
+                    out, add = self._zeros(op.x.numel, self.tdtype), None
+                    self._grads[("pact_dx", id(op))] = out
+                self._bwd.append(self._call("rn_pact_bwd", self.dtype, op.x.numel, self._p(self.act(op.x)),
+                                            self._p(dy), self._pp(op.gamma), self._p(out), self._p(add),
+                                            self._gp(op.gamma), self._p(self._pact_ws), sp))
+                self.param_done_at[op.gamma] = len(self._bwd)
             elif op.kind == "relu":
                 if op.x.needs_grad:
                     out, add = gs.contribute(op.x)

@@ -7,6 +7,8 @@ the reference function it mirrors, so checkpoints and parity fixtures are interc
   resnet_cifar10(...)  <-> symbol/resnet.py:123-148  (post-activation basic units)
   resnext(...)         <-> symbol/resnext.py:72-103  (grouped 3x3, BN on the shortcut)
   resnet_int8(...)     <-> symbol/resnet_int8.py:69-131 + int8_api.py:120-171 (fake-quant QAT)
+  resnet50_pact(...)   <-> the same structure with the activation quantizers of core/graph_optimize.py:184-187
+                           (PACT, learned clipping threshold) instead of Quantization_int8
   mobilenet(...)       <-> symbol/mobilenet.py:38-144    (MobileNet-v1: depthwise 3x3 + pointwise 1x1)
 The equivalence is checked against parameter counts and names restated from the reference
 (tests/test_symbol_plan.py) -- the reference files themselves are never imported.
@@ -143,18 +145,37 @@ def resnext(units, num_stage, filter_list, num_classes, data_type="float32", num
 
 
 # ----------------------------------------------------------------------------- int8 (QAT) graph
+def _nbits(bits):
+    return {} if bits is None else {"nbits": bits}  # (None: the operator's default, 8)
+
+
+def _pact(name, data, abits, pact_init):
+    """create_quant_node's PACT_CXX branch (core/graph_optimize.py:184-187): the threshold '<name>_gamma',
+    shape (1,), a trainable parameter initialised to `pact_init`."""
+    gamma = mx.sym.Variable(name=name + "_gamma", init=mx.init.Constant(pact_init))
+    return mx.sym.contrib.PACT(data=data, gamma=gamma, name=name, **_nbits(abits))
+
+
 def quant_conv(name, data, num_filter, kernel, stride, pad=(0, 0), no_bias=True, num_group=1, in_channels=None,
-               quant_mode="minmax", delay_quant=0, ema_decay=0.99, workspace=512):
+               quant_mode="minmax", delay_quant=0, ema_decay=0.99, workspace=512, act_op="Quantization_int8",
+               wbits=None, abits=None, pact_init=8.0):
     """int8_api.py:120-150 quant_conv_cxx: Quantization_int8 on the weight ('<name>_weight') and on
-    the data ('<name>_data') feeding a plain Convolution."""
+    the data ('<name>_data') feeding a plain Convolution. act_op="PACT": the data quantizer is
+    mx.sym.contrib.PACT with `abits` bits instead."""
+    assert act_op in ("Quantization_int8", "PACT"), act_op
     weight = mx.sym.Variable(name=name + "_weight", shape=(num_filter, in_channels // num_group) + tuple(kernel),
                              dtype="float32")
     weight_q = mx.sym.contrib.Quantization_int8(data=weight, name=name + "_weight", quant_mode=quant_mode,
                                                 is_weight=True, is_weight_perchannel=False, ema_decay=ema_decay,
-                                                delay_quant=delay_quant, grad_mode="ste", workspace=workspace)
-    data_q = mx.sym.contrib.Quantization_int8(data=data, name=name + "_data", quant_mode=quant_mode, is_weight=False,
-                                              is_weight_perchannel=False, ema_decay=ema_decay,
-                                              delay_quant=delay_quant, grad_mode="ste", workspace=workspace)
+                                                delay_quant=delay_quant, grad_mode="ste", workspace=workspace,
+                                                **_nbits(wbits))
+    if act_op == "PACT":
+        data_q = _pact(name + "_data", data, abits, pact_init)
+    else:
+        data_q = mx.sym.contrib.Quantization_int8(data=data, name=name + "_data", quant_mode=quant_mode,
+                                                  is_weight=False, is_weight_perchannel=False, ema_decay=ema_decay,
+                                                  delay_quant=delay_quant, grad_mode="ste", workspace=workspace,
+                                                  **_nbits(abits))
     kw = dict(name=name, data=data_q, num_filter=num_filter, kernel=kernel, stride=stride, pad=pad, no_bias=no_bias,
               weight=weight_q)
     if num_group != 1:
@@ -163,15 +184,21 @@ def quant_conv(name, data, num_filter, kernel, stride, pad=(0, 0), no_bias=True,
 
 
 def quant_fc(name, data, num_hidden, in_channels, quant_mode="minmax", delay_quant=0, ema_decay=0.99,
-             workspace=512):
-    """int8_api.py:152-171 quant_fc_cxx."""
+             workspace=512, act_op="Quantization_int8", wbits=None, abits=None, pact_init=8.0):
+    """int8_api.py:152-171 quant_fc_cxx (act_op="PACT": as quant_conv)."""
+    assert act_op in ("Quantization_int8", "PACT"), act_op
     weight = mx.sym.Variable(name=name + "_weight", shape=(num_hidden, in_channels), dtype="float32")
     fc_q = mx.sym.contrib.Quantization_int8(data=weight, name=name + "_weight", is_weight=True, ema_decay=ema_decay,
                                             delay_quant=delay_quant, quant_mode=quant_mode,
-                                            is_weight_perchannel=False, grad_mode="ste", workspace=workspace)
-    data_q = mx.sym.contrib.Quantization_int8(data=data, name=name + "_data", is_weight=False, ema_decay=ema_decay,
-                                              delay_quant=delay_quant, quant_mode=quant_mode,
-                                              is_weight_perchannel=False, grad_mode="ste", workspace=workspace)
+                                            is_weight_perchannel=False, grad_mode="ste", workspace=workspace,
+                                            **_nbits(wbits))
+    if act_op == "PACT":
+        data_q = _pact(name + "_data", data, abits, pact_init)
+    else:
+        data_q = mx.sym.contrib.Quantization_int8(data=data, name=name + "_data", is_weight=False,
+                                                  ema_decay=ema_decay, delay_quant=delay_quant, quant_mode=quant_mode,
+                                                  is_weight_perchannel=False, grad_mode="ste", workspace=workspace,
+                                                  **_nbits(abits))
     return mx.sym.FullyConnected(data=data_q, num_hidden=num_hidden, name=name, weight=fc_q)
 
 
@@ -194,19 +221,28 @@ def _int8_unit(x, cin, nf, stride, dim_match, name, bottle_neck, mom, qkw):
 
 def resnet_int8(units, num_stage, filter_list, num_classes, data_type="float32", bottle_neck=True, bn_mom=0.9,
                 workspace=512, memonger=False, grad_scale=1.0, dataset_type="imagenet", quant_mode="minmax",
-                delay_quant=0, ema_decay=0.99):
-    """symbol/resnet_int8.py:69-131 (the C5 config graph; BN stays separate)."""
+                delay_quant=0, ema_decay=0.99, act_op="Quantization_int8", wbits=None, abits=None, pact_init=8.0):
+    """symbol/resnet_int8.py:69-131 (the C5 config graph; BN stays separate). act_op="PACT": every
+    activation quantizer that reads a ReLU output -- all but conv0's, which stays Quantization_int8 on the
+    normalised image -- is mx.sym.contrib.PACT with `abits` bits; the weights stay Quantization_int8 (`wbits`)."""
     assert len(units) == num_stage
-    qkw = dict(quant_mode=quant_mode, delay_quant=delay_quant, ema_decay=ema_decay, workspace=workspace)
+    qkw0 = dict(quant_mode=quant_mode, delay_quant=delay_quant, ema_decay=ema_decay, workspace=workspace)
+    qkw = dict(qkw0)
+    if wbits is not None:
+        qkw0["wbits"] = qkw["wbits"] = wbits
+    if act_op != "Quantization_int8":
+        qkw.update(act_op=act_op, abits=abits, pact_init=pact_init)
+    elif abits is not None:
+        qkw0["abits"] = qkw["abits"] = abits
     data = mx.sym.Variable(name="data")
     data = mx.sym.identity(data=data, name="id")
     data = _bn(data, "bn_data", fix_gamma=True, eps=2e-5, mom=bn_mom)
     if dataset_type == "imagenet":
-        body = quant_conv("conv0", data, filter_list[0], (7, 7), (2, 2), (3, 3), in_channels=3, **qkw)
+        body = quant_conv("conv0", data, filter_list[0], (7, 7), (2, 2), (3, 3), in_channels=3, **qkw0)
         body = _relu(_bn(body, "bn0", mom=bn_mom), "relu0")
         body = mx.sym.Pooling(data=body, kernel=(3, 3), stride=(2, 2), pad=(1, 1), pool_type="max")
     else:
-        body = quant_conv("conv0", data, filter_list[0], (3, 3), (1, 1), (1, 1), in_channels=3, **qkw)
+        body = quant_conv("conv0", data, filter_list[0], (3, 3), (1, 1), (1, 1), in_channels=3, **qkw0)
     c = filter_list[0]
     for i in range(num_stage):
         st = (1, 1) if i == 0 else (2, 2)
@@ -268,6 +304,13 @@ def mobilenet_1_0(num_classes=1000):
 
 def resnet50_int8(num_classes=1000):
     return resnet_int8([3, 4, 6, 3], 4, [64, 256, 512, 1024, 2048], num_classes, "float32", True)
+
+
+def resnet50_pact(num_classes=1000, wbits=8, abits=4):
+    """ResNet-50 with PACT activation quantizers (the reference's setting: 4 bits, thresholds starting at 8.0)
+    and Quantization_int8 weights."""
+    return resnet_int8([3, 4, 6, 3], 4, [64, 256, 512, 1024, 2048], num_classes, "float32", True, act_op="PACT",
+                       wbits=wbits, abits=abits, pact_init=8.0)
 
 
 def resnet50(num_classes=1000):

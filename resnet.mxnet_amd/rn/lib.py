@@ -131,6 +131,9 @@ SIGNATURES = {
     "rn_quant_int8_expand": (_i32, [_i32, _i64, _P, _P, _P, _P]),
     "rn_weight_quant_pack": (_i32, [_P, _i32, _i32, _P, _P]),
     "rn_quant_int8_bwd": (_i32, [_i32, _i64, _P, _P, _P, _P, _i32, _P, _P]),
+    "rn_pact_fwd": (_i32, [_i32, _i64, _P, _P, _i32, _P, _P, _P, _P]),
+    "rn_pact_bwd_ws_bytes": (_i64, [_i64]),
+    "rn_pact_bwd": (_i32, [_i32, _i64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rn_set_tuning": (_i32, [_i32, _i32]),
     "rn_last_error": (C.c_char_p, []),
     "rn_version": (_i32, []),
