@@ -1601,9 +1601,9 @@ class Executor:
         if rmode not in ("", "0", "1"):
             raise L.RNError("RN_BN_BWD_RECOMPUTE=%r: 0, 1 or unset" % rmode)
         recompute_min_bytes = {"": self.RECOMPUTE_MIN_BYTES, "0": None, "1": 0}[rmode]
-        # (removed in round 6, measured neutral, its kernel kept and kernel-tested: a quantizer pair's clips folded
-        # into the later data gradient, RN_QUANT_PAIR_FUSION -- rn_conv_bwd_data_bnred_clip2; C5 22.68 / 22.69 vs
-        # 22.69 / 22.68 ms)
+        # (removed in round 6, measured neutral, its kernel kept and kernel-tested by tests/test_kernels_gpu.py::
+        # test_dgrad_quant_pair_clip_fold: a quantizer pair's clips folded into the later data gradient,
+        # RN_QUANT_PAIR_FUSION -- rn_conv_bwd_data_bnred_clip2; C5 22.68 / 22.69 vs 22.69 / 22.68 ms)
         # one workspace for the weight gradients' split-M partial tiles (rn_conv_bwd_filter_ws),
         # sized for the largest layer. Shared safely because every call using it is a weight-gradient
         # call, and those all run in plan order on ONE stream (the side stream when it is on:

@@ -25,6 +25,16 @@ clip_grad_quantization_int8.py:37-54), every weight quantizer's threshold, unit,
 (rn_weight_quant_pack) -- the int8 convolutions as exact fp64 sums of the device's own codes times
 the two units, and the straight-through clips folded into the BatchNorm backwards, the stem's and
 the FullyConnected input's.
+
+PACT (graphs with act_op="PACT"): every rn_pact_fwd bit for bit from its stored input and the gamma in the
+flat master buffer -- unit, values, and the int8 codes where it emits them (pact_fwd_torch, held to
+pact_util.pact_fwd_ref by tests/test_pact_cpu.py) --, the int8 convolutions behind the codes as for C5, and
+every rn_pact_bwd: dx bit for bit (with the add operand it accumulates in place for the second reader of a
+stage-first act1), dgamma within the kernel's own fp32 summation bound, in the gamma's own slot of the flat
+gradient buffer.
+
+Coverage is on record both ways: `skipped` counts the backward calls without a handler, `fwd_skipped` the
+forward plan ops no branch of check_forward checked; the tests assert both empty.
 """
 import types
 
@@ -162,6 +172,45 @@ def ema_refs(prev, cur, decay):
             float(f32(c * om + p * d))}
 
 
+def round_half_away(a):
+    """roundf as rn_pact_fwd writes it: trunc(a) + sign(a) * (|a - trunc(a)| >= 0.5). The subtraction is exact,
+    so there is no double rounding as in floor(|a| + 0.5) (_round_away above, which the int8 quantizers use)."""
+    t = torch.trunc(a)
+    return t + torch.sign(a) * ((a - t).abs() >= 0.5).to(a.dtype)
+
+
+def pact_fwd_torch(x, gamma, nbits, to_bf16=False):
+    """rn_pact_fwd on the fp32 tensor x (any device) with the fp32 threshold `gamma` (a Python float), the
+    arithmetic of pact_util.pact_fwd_ref restated in torch: unit = f32(gamma) / f32(2^nbits - 1), a =
+    min(x, gamma) / unit, q = round_half_away(a), value = q * unit, each one fp32 operation (f32 above), the
+    value rounded to bf16 where the storage is bf16; gamma <= 0: zeros. Returns (values fp32, codes fp32,
+    unit fp32 scalar tensor on the CPU). tests/test_pact_cpu.py holds the two restatements together."""
+    x = x.float()
+    g = torch.tensor(float(gamma), dtype=torch.float32)
+    unit = f32(g.double() / float(2 ** int(nbits) - 1))
+    if not float(unit) > 0.0:
+        z = torch.zeros_like(x)
+        return z, z.clone(), unit
+    gd, ud = g.to(x.device), unit.double().to(x.device)
+    c = torch.where(x < gd, x, gd)
+    q = round_half_away(f32(c.double() / ud))
+    v = f32(q.double() * ud)
+    return (_bf16(v) if to_bf16 else v), q, unit
+
+
+def pact_bwd_torch(x, dy, gamma, add=None, to_bf16=False):
+    """rn_pact_bwd (pact_util.pact_bwd_ref restated in torch): dx = store(dy * [x < gamma] + add), the add in
+    fp32 with one rounding to the storage type; dgamma = sum dy * [x >= gamma] in fp64 and the sum of those
+    terms' magnitudes. Returns (dx fp32, dgamma float, sum |terms| float)."""
+    x, dy = x.float(), dy.float()
+    keep = x < torch.tensor(float(gamma), dtype=torch.float32, device=x.device)
+    dx = torch.where(keep, dy, torch.zeros_like(dy))
+    if add is not None:
+        dx = dx + add.float()
+    clipped = torch.where(keep, torch.zeros_like(dy, dtype=torch.float64), dy.double())
+    return (_bf16(dx) if to_bf16 else dx), float(clipped.sum()), float(clipped.abs().sum())
+
+
 EXACT = {"mismatch": 0.0}  # bit-identical: the fraction of differing elements
 
 
@@ -173,6 +222,9 @@ class Checker:
         self.prev_aux = prev_aux or {}
         self.first_batch = first_batch
         self.rec = []  # (kind, layer, metrics dict, bar dict)
+        self.fwd_skipped = {}  # {plan op kind: ops of the forward that no branch of check_forward checked}
+        self.pact_stats = {}   # {PACT name: gamma, clipped fraction and highest code of the checked forward}
+        self.pact_bwd = []     # per rn_pact_bwd call: name, whether it had an add operand, whether that was dx
         self.byptr = {}
         for b in list(ex._acts.values()) + list(ex._grads.values()):
             self.byptr[b.data_ptr()] = b
@@ -267,6 +319,7 @@ class Checker:
     def check_forward(self):
         ex = self.ex
         bar = BF16_BAR if ex.dtype == 0 else F32_BAR
+        self.fwd_skipped = {}
         for op in ex.plan.ops:
             if getattr(op, "qweight", None) is not None:
                 self.check_weight_quant(op)
@@ -300,6 +353,8 @@ class Checker:
                 self.add(kind, op.name, self.act_nchw(op.y), y, bar)
             elif op.kind == "quant":
                 self.check_quant(op)
+            elif op.kind == "pact":
+                self.check_pact(op)
             elif op.kind == "add":
                 self.check_add(op, bar)
             elif op.kind == "relu":
@@ -307,33 +362,38 @@ class Checker:
                                 EXACT)
             elif op.kind == "stem" and op.bn is not None and op.quant is not None:
                 self.check_stem_quant(op, bar)
-            elif op.kind == "stem" and op.bn is not None and op.quant is None:
+            elif op.kind == "stem" and op.quant is None:
                 x = op.x
                 b = op.bnbuf
-                sc, sh = b[16:16 + x.c], b[24:24 + x.c]
                 data = ex._in_bufs[ex._in_idx].view(x.n, x.c, x.h, x.w).float()
-                # bn_data (fix_gamma): batch statistics of the NCHW input, biased variance
-                mean = data.double().mean(dim=(0, 2, 3))
-                var = data.double().var(dim=(0, 2, 3), unbiased=False)
-                inv = 1.0 / torch.sqrt(var + op.bn["eps"])
-                self.add_metric("bn_fwd", "bn_data", {"mean": float(((b[0:x.c].double() - mean).abs() /
-                                                                       torch.sqrt(var)).max()),
-                                                      "invstd": _maxr(b[8:8 + x.c], inv)},
-                                {"mean": 1e-5, "invstd": 1e-5})
-                want = data * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1)
+                if op.bn is not None:
+                    sc, sh = b[16:16 + x.c], b[24:24 + x.c]
+                    # bn_data (fix_gamma): batch statistics of the NCHW input, biased variance
+                    mean = data.double().mean(dim=(0, 2, 3))
+                    var = data.double().var(dim=(0, 2, 3), unbiased=False)
+                    inv = 1.0 / torch.sqrt(var + op.bn["eps"])
+                    self.add_metric("bn_fwd", "bn_data", {"mean": float(((b[0:x.c].double() - mean).abs() /
+                                                                           torch.sqrt(var)).max()),
+                                                          "invstd": _maxr(b[8:8 + x.c], inv)},
+                                    {"mean": 1e-5, "invstd": 1e-5})
+                    want = data * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1)
+                else:  # no bn_data before the first convolution (ResNeXt, MobileNet): the image itself, re-laid
+                    want = data
+                src = "bn_data" if op.bn is not None else op.name
                 k = op.y.c
                 if op.p4 is not None:  # the zero-bordered NHWC4 image, 8 x 8 taps of 4 channels
                     hp, wp = op.p4
                     x4 = op.x8.view(x.n, hp, wp, 4).permute(0, 3, 1, 2).float()
                     ph, pw = op.pad
-                    self.add("stem_prepare", "bn_data", x4[:, :x.c, ph:ph + x.h, pw:pw + x.w], _bf16(want), BF16_BAR)
+                    self.add("stem_prepare", src, x4[:, :x.c, ph:ph + x.h, pw:pw + x.w], _bf16(want), BF16_BAR)
                     w = op.wk.view(k, 8, 8, 4)[:, :op.kernel[0], :op.kernel[1], :].permute(0, 3, 1, 2).float()
                     y = ref_fwd(x4, w, op.stride, (0, 0))[:, :, :op.y.h, :op.y.w]
                 else:  # NHWC with 8 channels (3 real)
                     x8 = self.nchw(op.x8, x.n, x.h, x.w, 8, x.c)
-                    self.add("stem_prepare", "bn_data", x8, _bf16(want) if ex.dtype == 0 else want, bar)
+                    self.add("stem_prepare", src, x8, _bf16(want) if ex.dtype == 0 else want, bar)
                     y = ref_fwd(x8, self.w_from_krsc(op.wk, op.dfull), op.stride, op.pad)
-                self.add("conv_fwd", op.name, self.act_nchw(op.y), y, bar)
+                # (a stem without bn_data under a kind of its own: "conv_fwd" counts bn_data stems and convs)
+                self.add("conv_fwd" if op.bn is not None else "stem_conv_fwd", op.name, self.act_nchw(op.y), y, bar)
             elif op.kind == "bn" and not op.use_global_stats:
                 x = self.act_nchw(op.x).double()
                 c = op.x.c
@@ -380,6 +440,31 @@ class Checker:
                 g[torch.arange(x.n, device=g.device), lab] -= 1.0
                 dl = ex.grad_buf(x).view(x.n, x.cp)[:, :x.c]
                 self.add("softmax_grad", op.name, dl.float(), g * op.grad_scale, bar)
+            else:
+                # no branch above checks this op (an affine, a BatchNorm on its moving statistics, a stem
+                # without bn_data, a kind added since): on record, as the backward side's `skipped`
+                self.fwd_skipped[op.kind] = self.fwd_skipped.get(op.kind, 0) + 1
+
+    def check_pact(self, op):
+        """A PACT (rn_pact_fwd), bit for bit from the device's own stored input and the gamma in the flat
+        master buffer (read here, before the backward and the update): the unit, the values over the whole
+        buffer, and where it emits them the int8 codes (padded channels included). Its clipped fraction
+        mean(x >= gamma) and highest code go on record (pact_stats): a test's preconditions."""
+        ex = self.ex
+        x = ex.act(op.x).float()
+        gamma = float(ex.pview(op.gamma)[0])
+        val, code, unit = pact_fwd_torch(x, gamma, op.nbits, to_bf16=ex.dtype == 0)
+        m = {"unit": 0.0 if float(op.unit[0]) == float(unit) else 1.0,
+             "values": self.mismatch(ex.act(op.y).float(), val)["mismatch"]}
+        if op.codes is not None:
+            m["codes"] = self.mismatch(op.codes.float(), code)["mismatch"]
+        xr = self.act_nchw(op.x)
+        # (the highest code the DEVICE wrote: its codes, or its stored values over its unit -- q * unit / unit
+        # rounds back to the integer q at these widths, also after a bf16 rounding of the value (2^-9 q < 0.5))
+        top = op.codes.max() if op.codes is not None else torch.round(ex.act(op.y).float().max() / op.unit[0])
+        self.pact_stats[op.name] = {"gamma": gamma, "clipped": float((xr >= gamma).double().mean()),
+                                    "max_code": int(top), "codes": op.codes is not None}
+        self.add_metric("pact", op.name, m, {k: 0.0 for k in m})
 
     def check_add(self, op, bar):
         """Residual add (+ ReLU); with BatchNorms applied inside it (rn_bn_apply_add, the post-activation
@@ -833,6 +918,46 @@ class Checker:
                 ref = ref + state["add"][:n].float()
             ref = _bf16(ref) if self.ex.dtype == 0 else ref
             self.add_metric("quant_bwd", "ste", self.mismatch(self.t(dxp)[:n].float(), ref), EXACT)
+        return pre, post
+
+    def _h_rn_pact_bwd(self, args, state):
+        """A PACT's backward (rn_pact_bwd): dx bit for bit store(dy * [x < gamma] + add) -- dy and add taken
+        before the call, either may be the buffer dx overwrites --; dgamma, read from the PACT's own slot of the
+        flat gradient buffer, against the fp64 sum of dy * [x >= gamma] in units of the kernel's own summation
+        bound k * 2^-24 * sum |terms| (k = pact_util.pact_bwd_chain, from the launch geometry; bar 1), exactly 0
+        where nothing is clipped; and the slot the call's dgamma pointer addresses is that gamma's."""
+        from pact_util import pact_bwd_chain
+        n, xp, dyp, gmp, dxp, addp, dgp = args[1], args[2], args[3], args[4], args[5], args[6], args[7]
+        if not hasattr(self, "pact_by_gamma"):
+            self.pact_by_gamma = {self.ex._pp(o.gamma).value: o for o in self.ex.plan.ops if o.kind == "pact"}
+        op = self.pact_by_gamma[gmp.value]
+        call = {"name": op.name, "add": addp is not None, "aliased": addp is not None and addp.value == dxp.value}
+        self.pact_bwd.append(call)
+        sd, sa = self._snap(dyp, state, "dy"), self._snap(addp, state, "add")
+
+        def pre():
+            sd()
+            sa()
+
+        def post():
+            x = self.t(xp)[:n]
+            gamma = float(self.ex.pview(op.gamma)[0])
+            add = state["add"][:n] if state["add"] is not None else None
+            dx, dg, terms = pact_bwd_torch(x, state["dy"][:n], gamma, add, to_bf16=self.ex.dtype == 0)
+            try:
+                slot = self.grad_name(dgp)
+            except KeyError:
+                slot = None
+            dev = float(self.ex.gview(op.gamma)[0])
+            call["dgamma"] = dev
+            if terms > 0.0:
+                bound = pact_bwd_chain(n, x.element_size()) * 2.0 ** -24 * terms
+                edg = abs(dev - dg) / bound
+            else:
+                edg = 0.0 if dev == 0.0 else float("inf")
+            m = {"dx": self.mismatch(self.t(dxp)[:n].float(), dx)["mismatch"], "dgamma": edg,
+                 "slot": 0.0 if slot == op.gamma else 1.0}
+            self.add_metric("pact_bwd", op.name, m, {"dx": 0.0, "dgamma": 1.0, "slot": 0.0})
         return pre, post
 
     def _h_rn_eltwise_add(self, args, state):

@@ -3,6 +3,7 @@ PACT graph surface driven through the `mxnet` shim's public API.
 
   pact_fwd_ref / pact_bwd_ref   numpy float32 restatements of rn_pact_fwd / rn_pact_bwd, bit for bit
                                 (core/operator/PACT.py:102-144 with the arithmetic of include/rn.h)
+  edge_inputs                   the kernels' edge inputs: negatives, values above and equal to gamma, exact ties
   pact_bwd_chain                the longest chain of fp32 additions of rn_pact_bwd's dgamma at a given n
   PactProp                      a CustomOpProp registered as "PACT_PY" (core/operator/PACT.py:146-166)
   create_quant_node / attach_quantize_node
@@ -61,6 +62,18 @@ def pact_bwd_ref(x, dy, gamma, add=None, to_bf16=False):
         dx = (dx + np.asarray(add, dtype=np.float32)).astype(np.float32)
     clipped = np.where(keep, 0.0, dy.astype(np.float64))
     return (bf16(dx) if to_bf16 else dx), float(clipped.sum()), float(np.abs(clipped).sum())
+
+
+def edge_inputs(n, to_bf16, gamma, unit, seed):
+    """Negatives, values above gamma, elements equal to gamma, exact ties (odd multiples of unit / 2, both signs);
+    rounded to the storage type first, so that the restatement sees what the device reads."""
+    rng = np.random.RandomState(seed)
+    x = (rng.randn(n) * 0.6 * gamma).astype(np.float32)
+    x[rng.randint(0, n, size=max(n // 8, 2))] = gamma
+    k = rng.randint(-7, 2 * 15, size=max(n // 4, 4))
+    x[rng.randint(0, n, size=k.size)] = ((2 * k + 1) * (unit / 2)).astype(np.float32)
+    x[:6] = [gamma, unit / 2, 2 * gamma, -gamma / 3, 3 * (unit / 2), -5 * (unit / 2)]  # (whatever the draw gave)
+    return bf16(x) if to_bf16 else x
 
 
 def pact_bwd_chain(n, itemsize):

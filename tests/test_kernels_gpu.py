@@ -1449,6 +1449,98 @@ def test_bn_backward_quant_clip_fold(gpu, dtype, case):
     assert rel_err(dg2.cpu().numpy()[:c], dg_ref) < (1e-4 if dtype == F32 else 2e-2)
 
 
+@pytest.mark.parametrize("case", [
+    (2, 256, 14, 14, 64, 1, 1, 0),    # a stage-first conv1
+    (2, 256, 14, 14, 512, 1, 2, 0),   # a stage-first shortcut: 3 of 4 input positions get no gradient of their own
+    (3, 128, 13, 11, 96, 3, 1, 1),    # ragged rows and columns
+    (2, 64, 16, 16, 128, 3, 2, 1),    # the stride-2 3x3 data-gradient classes
+])
+def test_dgrad_quant_pair_clip_fold(gpu, case):
+    """rn_conv_bwd_data_bnred_clip2: the later data gradient of a stage-first unit's act1, which two
+    Quantization_int8 read (symbol/resnet_int8.py), with both straight-through clips and the BN+ReLU backward
+    reduction in its epilogue. (1) dx is bit for bit bf16([y < t1] * g + [y < t2] * other), y the stored bf16
+    BN+ReLU output, g what rn_conv_bwd_data stores for the same descriptor and operands (include/rn.h: bf16 of its
+    gradient, one rounding of the sum); (2) rn_bn_bwd_part on its partials with no clip == rn_bn_bwd with
+    clip / clip2 / dy2 over g (the path test_bn_backward_quant_pair_fold holds to the two quantizer backwards) and
+    == the oracle's BN backward of the stored dx * [y > 0]; (3) every partial row is written; (4) each threshold
+    clips, and not the same set."""
+    n, c, h, w, k, r, st, pd = case
+    rng = np.random.default_rng(33)
+    xb = bf16_round(rng.standard_normal((n, c, h, w)) * 1.5 + 0.3)
+    gamma, beta = rng.uniform(0.5, 1.5, c), rng.standard_normal(c) * 0.2
+    d = conv_desc(BF16, n, c, h, w, k, r, r, st, pd)
+    lib = L.load()
+    # what the entry requires: dense whole 8-channel chunks on an LDS-DMA tile (a case that left it must fail here)
+    assert d.c % 8 == 0 and d.c == d.c_real == c and lib.rn_conv_tile(C.byref(d), 1) >= 64
+    f = lambda a: torch.tensor(np.asarray(a, np.float64), dtype=torch.float32, device=gpu)
+    g_d, b_d, mm, mv = f(gamma), f(beta), f(np.zeros(c)), f(np.ones(c))
+    sm, si, sc, sh = [torch.zeros(c, dtype=torch.float32, device=gpu) for _ in range(4)]
+    bd = L.BNDesc(dtype=BF16, m=n * h * w, c=c, c_real=c, eps=1e-5, momentum=0.9, fix_gamma=0, relu=1)
+    ws = torch.zeros(lib.rn_bn_workspace_bytes(C.byref(bd)) // 4 + 16, dtype=torch.float32, device=gpu)
+    xbd = to_nhwc(xb, BF16, gpu)
+    act = torch.zeros_like(xbd)
+    L.call("rn_bn_fwd_train", C.byref(bd), p(xbd), p(act), p(g_d), p(b_d), p(mm), p(mv), p(sm), p(si), p(sc), p(sh),
+           p(ws), stream())
+    torch.cuda.synchronize()
+    a_np = from_nhwc(act, c)                                       # y: the stored BN+ReLU output
+    t1, t2 = (float(np.quantile(a_np[a_np > 0], qq)) for qq in (0.6, 0.8))
+    tq1, tq2 = (torch.tensor([t], dtype=torch.float32, device=gpu) for t in (t1, t2))
+    wt = bf16_round(rng.standard_normal((k, c, r, r)) / np.sqrt(c * r * r))
+    P, Q = ops.conv_out_hw(h, w, r, r, (st, st), (pd, pd))
+    dy = bf16_round(rng.standard_normal((n, k, P, Q)))
+    other = to_nhwc(rng.standard_normal((n, c, h, w)), BF16, gpu)  # the first quantizer's stored gradient
+    wc = torch.zeros(d.c * r * r * d.k_pad, dtype=torch.bfloat16, device=gpu)
+    L.call("rn_conv_weight_pack", C.byref(d), p(_master_krsc(wt, gpu)), None, p(wc), stream())
+    dyd = to_nhwc(dy, BF16, gpu)
+    g = torch.full_like(xbd, 55.0)
+    L.call("rn_conv_bwd_data", C.byref(d), p(dyd), p(wc), p(g), None, stream())
+    nrb = lib.rn_conv_bnred_blocks(C.byref(d))
+    part = torch.full((nrb * d.c * 2,), float("nan"), dtype=torch.float32, device=gpu)
+    dx = torch.full_like(xbd, 77.0)
+    L.call("rn_conv_bwd_data_bnred_clip2", C.byref(d), p(dyd), p(wc), p(dx), p(other), p(xbd), p(sm), p(sc), p(sh),
+           p(tq1), p(tq2), p(part), stream())
+    zf = lambda: torch.zeros(c, dtype=torch.float32, device=gpu)
+    bd0 = L.BNDesc(dtype=BF16, m=n * h * w, c=c, c_real=c, eps=1e-5, momentum=0.9, fix_gamma=0, relu=1)
+    dx2, dg2, db2 = torch.zeros_like(xbd), zf(), zf()
+    L.call("rn_bn_bwd_part", C.byref(bd0), p(part), nrb, p(xbd), p(dx), p(dx2), None, p(g_d), p(sm), p(si), p(sc),
+           p(sh), p(dg2), p(db2), p(ws), stream())
+    bdp = L.BNDesc(dtype=BF16, m=n * h * w, c=c, c_real=c, eps=1e-5, momentum=0.9, fix_gamma=0, relu=1,
+                   clip=tq1.data_ptr(), clip2=tq2.data_ptr(), dy2=other.data_ptr())
+    dx1, dg1, db1 = torch.zeros_like(xbd), zf(), zf()
+    L.call("rn_bn_bwd", C.byref(bdp), p(xbd), p(g), p(dx1), None, p(g_d), p(sm), p(si), p(sc), p(sh), p(dg1), p(db1),
+           p(ws), stream())
+    torch.cuda.synchronize()
+    # (4) the inputs: each threshold clips, and not the same set
+    y = act.float()
+    c1, c2 = y >= tq1, y >= tq2
+    assert c1.float().mean().item() >= 0.05 and c2.float().mean().item() >= 0.05
+    assert (c1 != c2).float().mean().item() >= 0.05
+    # (1) bit for bit
+    dact_ref, _ = ops.conv2d_bwd(np.zeros((n, c, h, w)), wt, dy, (st, st), (pd, pd))
+    assert rel_err(from_nhwc(g, c), dact_ref) < TOL[BF16]
+    zero = torch.zeros_like(y)
+    want = (torch.where(c1, zero, g.float()) + torch.where(c2, zero, other.float())).to(torch.bfloat16)
+    diff = (dx.view(torch.int16) != want.view(torch.int16))
+    print("case", case, "tile", lib.rn_conv_tile(C.byref(d), 1), "differing elements", int(diff.sum()), "of",
+          diff.numel())
+    assert not diff.any()
+    if st == 2 and r == 1:  # the positions off the stride grid: no gradient of their own, the other's clipped one
+        off_grid = torch.ones_like(c1)
+        off_grid[:, ::2, ::2, :] = False
+        assert not g[off_grid].any() and dx[off_grid].any()
+        assert torch.equal(dx[off_grid].float(), torch.where(c2, zero, other.float())[off_grid])
+    # (3) every partial row the reduction covers was written
+    assert not torch.isnan(part).any()
+    # (2) the finished BatchNorm backward against the composed path and against the oracle
+    for a_, b_, bar in ((dx2, dx1, 3e-2), (dg2, dg1, 2e-2), (db2, db1, 2e-2)):
+        assert rel_err(a_.float().cpu().numpy(), b_.float().cpu().numpy()) < bar
+    _, cache = ops.bn_train_fwd(xb, gamma, beta, 1e-5, False)
+    dx_ref, dg_ref, db_ref = ops.bn_train_bwd(from_nhwc(dx, c) * (a_np > 0), cache, False)
+    assert rel_err(from_nhwc(dx2, c), dx_ref) < 3e-2
+    assert rel_err(dg2.cpu().numpy(), dg_ref) < 2e-2
+    assert rel_err(db2.cpu().numpy(), db_ref) < 2e-2
+
+
 BIG_CASES = [
     # n, c, h, w, k, r, stride, pad: 256-row tiles (fwd when k >= 128, dgrad when c >= 128)
     (2, 128, 14, 14, 256, 3, 1, 1),

@@ -56,6 +56,10 @@ def test_mobilenet_bf16_layerwise(gpu):
     # the calls that run them were hooked, not passed over
     assert not {"rn_conv_bwd_data", "rn_conv_bwd_filter_ws", "rn_conv_bwd_filter"} & set(ck.skipped), ck.skipped
     assert ck.covered.get("rn_conv_bwd_filter_ws", 0) >= 13
+    # every forward op was checked, conv_1 (a stem without bn_data) included: the checker re-lays the image
+    # itself for it; test_mobilenet_bf16_stem below holds it to the oracle at two widths besides
+    assert not ck.fwd_skipped, ck.fwd_skipped
+    assert len(by_kind.get("stem_conv_fwd", ())) == 1, by_kind.get("stem_conv_fwd")
     assert len(by_kind.get("conv_fwd", ())) == 13  # the pointwise layers
     bad = ck.failures()
     assert not bad, bad[:10]
@@ -63,8 +67,8 @@ def test_mobilenet_bf16_layerwise(gpu):
 
 def test_mobilenet_bf16_stem(gpu):
     """conv_1: 3x3 / stride 2 over the 3 input channels with no BatchNorm before it, a stem shape of its own
-    (the layerwise checker covers only stems behind bn_data). Against the oracle's convolution of the
-    bf16-rounded input and weights, the kernels' bar (1.5e-2 of max |ref|)."""
+    (the layerwise checker re-computes it from the device's own re-laid image at one width). Against the oracle's
+    convolution of the bf16-rounded input and weights, the kernels' bar (1.5e-2 of max |ref|)."""
     import mxnet as mx
     from gpu_util import bf16_round
     rng = np.random.default_rng(3)

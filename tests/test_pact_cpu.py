@@ -210,6 +210,49 @@ def test_no_batchnorm_fusion_crosses_a_pact(monkeypatch):
                 assert ex.wd_mult[ex.param_order.index(op.gamma)] == 1.0
 
 
+# ----------------------------------------------------------------------------- 3b. the two restatements agree
+@pytest.mark.parametrize("with_add", [False, True])
+@pytest.mark.parametrize("nbits", [4, 7, 8])
+@pytest.mark.parametrize("to_bf16", [False, True], ids=["fp32", "bf16"])
+def test_layerwise_restatement_equals_the_kernel_tests(to_bf16, nbits, with_add):
+    """tests/layerwise.py restates rn_pact_fwd / rn_pact_bwd in torch (pact_fwd_torch / pact_bwd_torch, what the
+    layer-by-layer checker holds the device to); the kernel tests hold the device to pact_util.pact_fwd_ref /
+    pact_bwd_ref in numpy. The two must not drift apart: equal element for element on the kernel tests' edge
+    inputs (negatives, values above gamma, elements equal to gamma, exact ties of both signs), with a gamma whose
+    4-bit unit is exact (7.5) and one whose unit is rounded (1.25), and for a non-positive gamma."""
+    import torch
+    from layerwise import pact_bwd_torch, pact_fwd_torch
+    n = 1001 * 48 + 3
+    for gamma in (np.float32(7.5), np.float32(1.25)):
+        unit = np.float32(gamma / np.float32(2 ** nbits - 1))
+        x = U.edge_inputs(n, to_bf16, gamma, unit, seed=n + nbits)
+        assert (x < 0).any() and (x > gamma).any() and (x == gamma).any()
+        a = x[x < gamma] / unit
+        ties = np.abs(a - np.trunc(a)) == 0.5
+        if nbits == 4 and gamma == np.float32(7.5):
+            assert (ties & (a > 0)).sum() >= 2 and (ties & (a < 0)).sum() >= 2  # (exact ties of both signs are in)
+        want, wcodes, wunit = U.pact_fwd_ref(x, gamma, nbits, to_bf16=to_bf16)
+        val, codes, tunit = pact_fwd_torch(torch.from_numpy(x), float(gamma), nbits, to_bf16=to_bf16)
+        assert np.float32(tunit.item()) == wunit and tunit.dtype == torch.float32
+        assert np.array_equal(val.numpy(), want) and val.dtype == torch.float32
+        assert np.array_equal(codes.numpy(), wcodes)
+        assert codes.max().item() == 2 ** nbits - 1 and (val.numpy()[x < 0] < 0).any()
+        rng = np.random.RandomState(7 + nbits)
+        rd = U.bf16 if to_bf16 else (lambda v: v)
+        dy = rd(rng.randn(n).astype(np.float32))
+        add = rd(rng.randn(n).astype(np.float32)) if with_add else None
+        wdx, wdg, wabs = U.pact_bwd_ref(x, dy, gamma, add, to_bf16=to_bf16)
+        dx, dg, terms = pact_bwd_torch(torch.from_numpy(x), torch.from_numpy(dy), float(gamma),
+                                       None if add is None else torch.from_numpy(add), to_bf16=to_bf16)
+        assert np.array_equal(dx.numpy(), wdx) and wabs > 0
+        assert abs(terms - wabs) <= 1e-12 * wabs and abs(dg - wdg) <= 1e-12 * wabs  # (fp64 sums, any order)
+    for gamma in (0.0, -1.0):
+        val, codes, tunit = pact_fwd_torch(torch.from_numpy(x), gamma, nbits, to_bf16=to_bf16)
+        want, wcodes, wunit = U.pact_fwd_ref(x, gamma, nbits, to_bf16=to_bf16)
+        assert not val.numpy().any() and not codes.numpy().any() and not want.any() and not wcodes.any()
+        assert np.float32(tunit.item()) == wunit
+
+
 # ----------------------------------------------------------------------------- 4. a step on mx.cpu()
 @pytest.fixture(scope="module")
 def unit_case():

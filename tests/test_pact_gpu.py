@@ -1,6 +1,7 @@
 """PACT on the MI355X: rn_pact_fwd / rn_pact_bwd against their numpy float32 restatements (tests/pact_util.py), the
-plan's int8 routing, and a training step of a small PACT network against the fp64 restatement replaying the device's
-own discrete decisions."""
+plan's int8 routing, a training step of a small PACT network against the fp64 restatement replaying the device's
+own discrete decisions, and every kernel of a step of a two-units-per-stage PACT network layer by layer
+(tests/layerwise.py)."""
 import ctypes as C
 
 import numpy as np
@@ -31,15 +32,7 @@ def _load(t):
 
 
 def _inputs(n, dtype, gamma, unit, seed):
-    """Negatives, values above gamma, elements equal to gamma, exact ties (odd multiples of unit / 2, both signs);
-    rounded to the storage type first, so that the restatement sees what the device reads."""
-    rng = np.random.RandomState(seed)
-    x = (rng.randn(n) * 0.6 * gamma).astype(np.float32)
-    x[rng.randint(0, n, size=max(n // 8, 2))] = gamma
-    k = rng.randint(-7, 2 * 15, size=max(n // 4, 4))
-    x[rng.randint(0, n, size=k.size)] = ((2 * k + 1) * (unit / 2)).astype(np.float32)
-    x[:6] = [gamma, unit / 2, 2 * gamma, -gamma / 3, 3 * (unit / 2), -5 * (unit / 2)]  # (whatever the draw gave)
-    return U.bf16(x) if dtype == BF16 else x
+    return U.edge_inputs(n, dtype == BF16, gamma, unit, seed)
 
 
 def _fwd(dev, dtype, x, gamma, nbits, want_codes, want_out=True):
@@ -328,3 +321,71 @@ def test_attached_graph_trains_and_checkpoints_on_gpu(gpu, tmp_path, monkeypatch
     assert plans["PACT"] == plans["PACT_CXX"] and sum(1 for o in plans["PACT"] if o[0] == "pact") == 19
     assert sum(1 for o in plans["PACT"] if o[0] == "conv" and o[2]) == 20  # every conv but the skipped first
     np.testing.assert_allclose(probs["PACT"], probs["PACT_CXX"], atol=0.05)
+
+
+# ----------------------------------------------------------------------------- 7. the network, layer by layer
+def _pact_net(abits):
+    """Two bottleneck units per stage: the smallest resnet_int8 graph with every unit form -- a stage-first unit
+    whose act1 two PACTs read (conv1's and the shortcut's) at stride 1 and at stride 2, identity units, stage 1's
+    64 -> 64 3x3, the pooled fc input. 29 PACTs, conv0 + 28 PACT-fed convolutions + fc1. pact_init = 1.0: at the
+    default 8.0 no element of this initialisation is clipped (PACT)."""
+    from rn import graphs
+    return graphs.resnet_int8([2, 2, 2, 2], 4, [64, 256, 512, 1024, 2048], 1000, "float32", True, act_op="PACT",
+                              wbits=8, abits=abits, pact_init=1.0)
+
+
+@pytest.mark.parametrize("precision,abits,warm", [("bfloat16", 4, 1), ("bfloat16", 8, 1), ("float32", 4, 0)],
+                         ids=["bf16_a4", "bf16_a8", "fp32_a4"])
+def test_pact_network_layerwise(gpu, monkeypatch, precision, abits, warm):
+    """Every kernel of one training step of the PACT network at 8 x 64 x 64 against its recompute from the
+    device's own inputs (tests/layerwise.py): each rn_pact_fwd bit for bit (unit, values, int8 codes), the int8
+    MFMA convolutions behind the 4-bit codes (stride-2 3x3, stride-2 1x1 shortcut, stage 1's 3x3) as exact sums
+    of the device's codes, bf16 storage of the 8-bit values, each rn_pact_bwd's dx bit for bit -- the second
+    reader of a stage-first act1 accumulating in place -- and its dgamma within the kernel's summation bound, in
+    its own slot of the flat gradient buffer. lr = 0.001 for the warm step: at 0.1 it throws the thresholds to
+    -1.8 .. 3.1 (three non-positive, one PACT clipping everything)."""
+    from test_step_bf16_gpu import _layerwise
+    monkeypatch.delenv("RN_INT8_MFMA", raising=False)
+    ck = _layerwise(_pact_net(abits), 8, 64, precision, warm=warm, lr=0.001)
+    # routing, before the numbers
+    convs = [op for op in ck.ex.plan.ops if op.kind == "conv"]
+    pacts = [op for op in ck.ex.plan.ops if op.kind == "pact"]
+    assert len(convs) == 28 and len(pacts) == 29
+    if abits == 4:
+        assert all(op.int8 and op.qsrc.kind == "pact" for op in convs)
+        assert [op.name for op in pacts if op.codes is None] == ["fc1_data"]
+    else:
+        assert not any(op.int8 for op in convs) and not any(op.codes is not None for op in pacts)
+    assert not ck.skipped, ck.skipped
+    assert not ck.fwd_skipped, ck.fwd_skipped
+    # the inputs exercise the clip path (conditions on the inputs, sized from the fp32 CPU executor: 2.4 % ..
+    # 16.9 % clipped per PACT, gammas 0.972 .. 1.021 after the warm step)
+    assert sorted(ck.pact_stats) == sorted(op.name for op in pacts)
+    st = ck.pact_stats
+    print("clipped fraction %.4f .. %.4f, gamma %.4f .. %.4f, lowest top code %d" % (
+        min(s["clipped"] for s in st.values()), max(s["clipped"] for s in st.values()),
+        min(s["gamma"] for s in st.values()), max(s["gamma"] for s in st.values()),
+        min(s["max_code"] for s in st.values())))
+    bad = {k: s for k, s in st.items() if not 0.01 <= s["clipped"] <= 0.5}
+    assert not bad, bad
+    bad = {k: s for k, s in st.items() if not 0.5 < s["gamma"] < 1.5}
+    assert not bad, bad
+    if abits == 4:
+        assert all(s["max_code"] == 15 for s in st.values()), st
+    if warm:
+        assert all(s["gamma"] != 1.0 for s in st.values()), st
+    else:
+        assert all(s["gamma"] == 1.0 for s in st.values()), st
+    assert len(ck.pact_bwd) == 29 and all(c["dgamma"] != 0.0 for c in ck.pact_bwd), ck.pact_bwd
+    # the numbers
+    bad = ck.failures()
+    assert not bad, bad[:10]
+    count = lambda kind: sum(1 for r in ck.rec if r[0] == kind)  # noqa: E731
+    assert count("pact") == 29
+    assert ck.covered["rn_pact_bwd"] == 29 and count("pact_bwd") == 29
+    assert count("weight_quant") == 30  # conv0, 28 convolutions, fc1
+    assert count("conv_fwd_i8") == (28 if abits == 4 else 0)
+    assert count("conv_fwd") == (1 if abits == 4 else 29)  # (conv0 in the stem, always on the values)
+    # the second reader of each stage-first act1 adds into the gradient the first one wrote
+    with_add = [c for c in ck.pact_bwd if c["add"]]
+    assert len(with_add) >= 4 and all(c["aliased"] for c in with_add), ck.pact_bwd

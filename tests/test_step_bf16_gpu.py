@@ -129,12 +129,12 @@ def test_resnet50_bf16_full_size_gradients(gpu):
     assert abs(ce_loss(res["prob"][0], label) - ce_loss(prob, label)) < 0.01 * ce_loss(prob, label)
 
 
-def _layerwise(sym, n, image, precision, tune=None, warm=0):
+def _layerwise(sym, n, image, precision, tune=None, warm=0, lr=0.1):
     """One training step (forward + backward, serialised on one stream) with every kernel checked
     against its fp32 torch restatement from the device's own inputs (tests/layerwise.py). warm: full
     steps (forward, backward, SGD update + the weight repacks after it) run before the checked one, so
     the checked forward reads weights the post-update packs wrote and quantizer states that follow
-    the EMA."""
+    the EMA. lr: the SGD learning rate of those warm steps."""
     import json
     import os
     import mxnet as mx
@@ -152,7 +152,7 @@ def _layerwise(sym, n, image, precision, tune=None, warm=0):
         mx.random.seed(2)
         mod.init_params(mx.init.Xavier(rnd_type="gaussian", factor_type="in", magnitude=2))
         mod.init_optimizer(kvstore="device", optimizer="sgd",
-                           optimizer_params={"learning_rate": 0.1, "wd": 1e-4, "momentum": 0.9})
+                           optimizer_params={"learning_rate": lr, "wd": 1e-4, "momentum": 0.9})
         ex = mod.executor
         ex.side_enabled = False  # the checks read buffers between calls: one stream, in plan order
         batch = mx.io.DataBatch(data=[mx.nd.array(data)], label=[mx.nd.array(label)])
@@ -178,11 +178,12 @@ def _layerwise(sym, n, image, precision, tune=None, warm=0):
         print("%-16s %4d checked, worst: %s" % (kind, e["n"], ", ".join(
             "%s %.2e (%s)" % (k, v[0], v[1]) for k, v in sorted(e.items()) if k != "n")))
     print("backward calls checked:", ck.covered, "not checked:", ck.skipped)
+    print("forward ops not checked:", ck.fwd_skipped)
     out = os.environ.get("RN_LAYERWISE_OUT")
     if out:
         with open(out, "w") as f:
             json.dump({"config": [n, image, precision], "records": ck.rec, "covered": ck.covered,
-                       "skipped": ck.skipped}, f)
+                       "skipped": ck.skipped, "fwd_skipped": ck.fwd_skipped}, f)
     return ck
 
 
@@ -198,6 +199,7 @@ def test_resnet50_bf16_full_size_layerwise(gpu):
     from rn import graphs
     ck = _layerwise(graphs.resnet50(), 256, 224, "bfloat16")
     assert not ck.skipped, ck.skipped
+    assert not ck.fwd_skipped, ck.fwd_skipped
     kinds = {r[0] for r in ck.rec}
     assert {"conv_fwd", "dgrad", "dgrad_bnred", "wgrad", "bn_fwd", "bn_bwd_dx", "bn_bwd_params", "stem_prepare",
             "pool_fwd", "pool_bwd", "fc_fwd", "softmax", "softmax_grad", "bn_apply", "fc_bias_grad", "stem_dbeta"} <= kinds, kinds
@@ -223,6 +225,7 @@ def _c4_layerwise(n, image):
     from rn import graphs
     ck = _layerwise(graphs.resnext50_32x4d(), n, image, "bfloat16", warm=1)
     assert not ck.skipped, ck.skipped
+    assert not ck.fwd_skipped, ck.fwd_skipped
     kinds = {r[0] for r in ck.rec}
     # (the grouped data gradients carry their BN-backward reduction: direct kernel or block-diagonal tile)
     # (every unit tail's backward in rn_relu_bwd_bnred)
@@ -254,6 +257,7 @@ def _c5_layerwise(n, image):
     from rn import graphs
     ck = _layerwise(graphs.resnet50_int8(), n, image, "bfloat16", warm=1)
     assert not ck.skipped, ck.skipped
+    assert not ck.fwd_skipped, ck.fwd_skipped
     kinds = {r[0] for r in ck.rec}
     assert {"conv_fwd_i8", "quant", "weight_quant", "dgrad_bnred", "bn_bwd_dx", "bn_bwd_params", "wgrad",
             "quant_bwd", "stem_dbeta", "fc_fwd"} <= kinds, kinds
@@ -289,6 +293,7 @@ def test_resnet50_fp32_layerwise(gpu):
     from rn import graphs
     ck = _layerwise(graphs.resnet50(), 4, 64, "float32")
     assert not ck.skipped, ck.skipped
+    assert not ck.fwd_skipped, ck.fwd_skipped
     bad = ck.failures()
     assert not bad, bad[:10]
 
