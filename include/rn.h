@@ -595,7 +595,7 @@ typedef struct rn_wquant_item {
  * w_crsk (channels >= c_real, columns >= k) is not written (zero from their first pack). */
 int rn_weight_quant_pack(const rn_wquant_item* items, int32_t count, int32_t dtype, float* ws,
                          rn_stream_t stream);
-/* STE backward: dx = dy (weights) or dy * (|x| <= t) (activations). */
+/* STE backward: dx = dy (weights) or dy * (|x| < t) (activations; the boundary excluded). */
 int rn_quant_int8_bwd(int32_t dtype, int64_t n, const void* x, const void* dy, void* dx,
                       const float* minmax, int32_t is_weight, const void* add_src,
                       rn_stream_t stream);
@@ -620,6 +620,61 @@ int64_t rn_pact_bwd_ws_bytes(int64_t n);
  * lane order): no atomics, bit-identical from run to run. No gradient flows through unit. dx may alias dy or add_src. x / dy / dx / add_src 16-byte aligned; any n. */
 int rn_pact_bwd(int32_t dtype, int64_t n, const void* x, const void* dy, const float* gamma, void* dx,
                 const void* add_src, float* dgamma, void* ws, rn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * GDRQ -- quantization with a mean-based clipping threshold and a symmetric signed code:
+ * mx.sym.contrib.GDRQ and mx.sym.Custom(op_type="GDRQ_PY") (core/graph_optimize.py:188-195,
+ * core/operator/GDRQ.py:50-190), per-tensor form (group_size = -1). alpha: DEVICE pointer to the
+ * threshold, an auxiliary state (fp32, shape (1,)), read by the kernels at run time.
+ * L = 2^nbits - 1 for weights and activations, unit = alpha / L (one fp32 division),
+ * c = min(max(x, -alpha), alpha), q = roundf(c / unit) in -L .. L, value = q * unit rounded to the
+ * storage type. alpha <= 0: zeros. The threshold update, every operation rounded to fp32 on its own:
+ * thr = ktimes * (sum|x| / (float)count); weights: alpha = thr; activations:
+ * alpha = alpha + lamda * (alpha - thr) (the reference's sign).
+ * ------------------------------------------------------------------------------------- */
+/* Workspace of rn_gdrq_fwd with update: one fp32 partial per block of a grid that depends on n only. */
+int64_t rn_gdrq_ws_bytes(int64_t n);
+/* Activation forward. update = 0 (fix_alpha, or inference): alpha is read only; one streaming launch.
+ * update = 1: first sum|x| over all n elements (padded channels hold zeros) as one partial per block,
+ * then one small launch adds the partials in index order (32 consecutive partials per lane of one wave,
+ * then the 64 lane sums in lane order), divides by n_real -- the element count without padding,
+ * 0 < n_real <= n --, applies the activation update and writes alpha and unit; then the quantize pass,
+ * which reads alpha from device memory (no host synchronisation, no atomics: bit-identical from run to
+ * run). out: the values (nullable only with codes). codes (nullable): the signed int8 q, n a multiple of
+ * 16, nbits <= 7 (else -1). unit (nullable): receives alpha / L. ws: rn_gdrq_ws_bytes(n), update only.
+ * x / out / codes 16-byte aligned; any n without codes. */
+int rn_gdrq_fwd(int32_t dtype, int64_t n, int64_t n_real, const void* x, float* alpha, int32_t nbits,
+                int32_t update, float ktimes, float lamda, void* out, void* codes, float* unit, void* ws,
+                rn_stream_t stream);
+/* Activation backward: dx = dy * [|x| <= alpha], the boundary INCLUDED (core/operator/GDRQ.py:132;
+ * rn_quant_int8_bwd excludes it), (+ add_src, nullable; the add in fp32, then rounded). Weights are
+ * straight-through and need no kernel. dx may alias dy or add_src. 16-byte aligned pointers; any n. */
+int rn_gdrq_bwd(int32_t dtype, int64_t n, const void* x, const void* dy, const float* alpha, void* dx,
+                const void* add_src, rn_stream_t stream);
+/* One weight of rn_weight_gdrq_pack: the fp32 master (KRSC, c_real channels) of a GDRQ weight and the
+ * copies written from it. */
+typedef struct rn_wgdrq_item {
+  const float* master; /* k * rs * c_real fp32                                              */
+  float* qw;           /* fake-quantized copy q * unit, master layout (required)            */
+  float* unit;         /* nullable: alpha / L                                               */
+  float* alpha;        /* the threshold state: written (:= thr) unless fix_alpha, then read */
+  int8_t* w_codes;     /* nullable: int8 q CLIPPED to -L .. L, KRSC, channel stride c       */
+  void* w_krsc;        /* nullable: forward compute copy of qw, KRSC with channel stride c
+                        * (rn_conv_weight_pack's w_krsc), dtype of the call                 */
+  void* w_crsk;        /* nullable: data-gradient compute copy of qw, dense CRSK with k_pad
+                        * stride (rn_conv_weight_pack's w_crsk), dtype of the call          */
+  int32_t k, rs, c_real, c, k_pad, nbits, fix_alpha;
+  float ktimes;
+} rn_wgdrq_item;
+/* Workspace of rn_weight_gdrq_pack: 64 block partials and the threshold of each of count weights. */
+int64_t rn_weight_gdrq_ws_bytes(int32_t count);
+/* Every GDRQ weight of a network in three launches: sum|w| of each tensor as 64 block partials (a
+ * thread adds its elements in index order; no atomics), then per weight the partials added in block
+ * order, the threshold and the unit, then the copies. Deterministic: bit-identical from run to run.
+ * items: DEVICE array of count entries; ws: rn_weight_gdrq_ws_bytes(count). The padding of w_codes /
+ * w_krsc / w_crsk (channels >= c_real, columns >= k) is not written (the buffers start zeroed). */
+int rn_weight_gdrq_pack(const rn_wgdrq_item* items, int32_t count, int32_t dtype, float* ws,
+                        rn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Runtime.

@@ -685,6 +685,152 @@ __global__ __launch_bounds__(64) void pact_dgamma_kernel(const float* __restrict
   }
 }
 
+// ---- GDRQ (core/operator/GDRQ.py:50-190, GDRQ_PY, per-tensor form): c = clip(x, -alpha, alpha),
+// q = round(c / unit), value = q * unit with unit = alpha / (2^nbits - 1): a symmetric signed code. alpha is an
+// auxiliary state read from device memory by every launch; with update it is first moved towards
+// ktimes * mean|x| by gdrq_abssum_kernel + gdrq_alpha_kernel (no atomics: bit-identical from run to run).
+__device__ __forceinline__ float gdrq_code(float x, float a, float unit) {
+  const float c = fminf(fmaxf(x, -a), a);
+  return unit > 0.f ? roundf(c / unit) : 0.f;
+}
+// the values only: 16-byte chunks, then the tail (any n)
+template <typename T>
+__global__ __launch_bounds__(256) void gdrq_values_kernel(int64_t n, const T* __restrict__ x, T* __restrict__ out,
+                                                          const float* __restrict__ alpha, float levels,
+                                                          float* __restrict__ unit_out) {
+  const float a = *alpha;
+  const float unit = a / levels;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && unit_out) *unit_out = unit;
+  constexpr int CE = 16 / sizeof(T);
+  const int64_t nc = n / CE;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nc; i += (int64_t)gridDim.x * blockDim.x) {
+    float f[CE];
+    chunk_to_f(reinterpret_cast<const uint4*>(x)[i], f, (const T*)nullptr);
+#pragma unroll
+    for (int e = 0; e < CE; ++e) f[e] = gdrq_code(f[e], a, unit) * unit;
+    reinterpret_cast<uint4*>(out)[i] = f_to_chunk(f, (const T*)nullptr);
+  }
+  for (int64_t i = nc * CE + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = from_f<T>(gdrq_code(to_f(x[i]), a, unit) * unit);
+}
+// the values (out nullable) AND their signed int8 codes -L .. L (nbits <= 7), 16 elements (one 16-byte code
+// chunk) per thread as pact_codes_kernel
+template <typename T>
+__global__ __launch_bounds__(256) void gdrq_codes_kernel(int64_t nchunk, const T* __restrict__ x, T* __restrict__ out,
+                                                         int8_t* __restrict__ codes, const float* __restrict__ alpha,
+                                                         float levels, float* __restrict__ unit_out) {
+  const float a = *alpha;
+  const float unit = a / levels;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && unit_out) *unit_out = unit;
+  constexpr int CE = 16 / sizeof(T);
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nchunk; i += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t cw[4];
+#pragma unroll
+    for (int h = 0; h < 16 / CE; ++h) {
+      float f[CE];
+      chunk_to_f(reinterpret_cast<const uint4*>(x)[i * (16 / CE) + h], f, (const T*)nullptr);
+#pragma unroll
+      for (int e = 0; e < CE; ++e) {
+        const float q = gdrq_code(f[e], a, unit);
+        f[e] = q * unit;
+        const int j = h * CE + e;
+        const uint32_t b = (uint32_t)(uint8_t)(int8_t)(int)q;
+        if ((j & 3) == 0) cw[j >> 2] = b;
+        else cw[j >> 2] |= b << (8 * (j & 3));
+      }
+      if (out) reinterpret_cast<uint4*>(out)[i * (16 / CE) + h] = f_to_chunk(f, (const T*)nullptr);
+    }
+    reinterpret_cast<uint4*>(codes)[i] = make_uint4(cw[0], cw[1], cw[2], cw[3]);
+  }
+}
+// sum |x|, the block's share: fp32 per-thread sums in element order, the wave butterfly, the four waves through
+// LDS, one partial per block (the geometry of pact_bwd_kernel; a function of n only)
+constexpr int kGdrqMaxBlocks = 2048;
+static inline int gdrq_sum_blocks(int64_t n) {  // (rn_gdrq_ws_bytes)
+  return (int)std::min<int64_t>(std::max<int64_t>((n + 2047) / 2048, 1), kGdrqMaxBlocks);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void gdrq_abssum_kernel(int64_t n, const T* __restrict__ x,
+                                                          float* __restrict__ part) {
+  constexpr int CE = 16 / sizeof(T);
+  const int64_t nc = n / CE;  // 16-byte chunks, then the tail
+  float s = 0.f;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nc; i += (int64_t)gridDim.x * blockDim.x) {
+    float f[CE];
+    chunk_to_f(reinterpret_cast<const uint4*>(x)[i], f, (const T*)nullptr);
+#pragma unroll
+    for (int e = 0; e < CE; ++e) s += fabsf(f[e]);
+  }
+  for (int64_t i = nc * CE + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    s += fabsf(to_f(x[i]));
+  s = wave_sum(s);
+  __shared__ float ws[4];
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+}
+// the block partials added in index order in pact_dgamma_kernel's fixed two-level shape (32 consecutive partials
+// per lane of one wave, then the 64 lane sums in lane order), then the threshold update of an activation:
+// thr = ktimes * (sum / count), alpha += lamda * (alpha - thr) -- the reference's sign -- each operation rounded
+// to fp32 on its own (no contraction: the restatements in the tests apply them one by one)
+__global__ __launch_bounds__(64) void gdrq_alpha_kernel(const float* __restrict__ part, int nblk, float count,
+                                                        float ktimes, float lamda, float levels,
+                                                        float* __restrict__ alpha, float* __restrict__ unit_out) {
+  static_assert(kGdrqMaxBlocks == 64 * 32, "one wave, 32 partials per lane");
+  const int lane = threadIdx.x;
+  float v[32];
+#pragma unroll
+  for (int j = 0; j < 32; ++j) {
+    const int i = lane * 32 + j;
+    v[j] = i < nblk ? part[i] : 0.f;
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < 32; ++j) s += v[j];
+  __shared__ float ls[64];
+  ls[lane] = s;
+  __syncthreads();
+  if (lane == 0) {
+#pragma clang fp contract(off)
+    float t = 0.f;
+#pragma unroll
+    for (int l = 0; l < 64; ++l) t += ls[l];
+    const float thr = ktimes * (t / count);
+    const float a0 = *alpha;
+    const float d = a0 - thr;
+    const float step = lamda * d;
+    const float a = a0 + step;
+    *alpha = a;
+    if (unit_out) *unit_out = a / levels;
+  }
+}
+// backward of an activation: dx = dy * [|x| <= alpha], the boundary included as the reference's
+// abs(data) <= alpha (rn_quant_int8_bwd's is strict), (+ add, in fp32, then rounded). dx may alias dy or add
+template <typename T>
+__global__ __launch_bounds__(256) void gdrq_bwd_kernel(int64_t n, const T* __restrict__ x, const T* dy, T* dx,
+                                                       const float* __restrict__ alpha, const T* add) {
+  const float a = *alpha;
+  constexpr int CE = 16 / sizeof(T);
+  const int64_t nc = n / CE;  // 16-byte chunks, then the tail
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nc; i += (int64_t)gridDim.x * blockDim.x) {
+    float fx[CE], fd[CE], fa[CE];
+    chunk_to_f(reinterpret_cast<const uint4*>(x)[i], fx, (const T*)nullptr);
+    chunk_to_f(reinterpret_cast<const uint4*>(dy)[i], fd, (const T*)nullptr);
+    if (add) chunk_to_f(reinterpret_cast<const uint4*>(add)[i], fa, (const T*)nullptr);
+#pragma unroll
+    for (int e = 0; e < CE; ++e) {
+      const float g = fabsf(fx[e]) <= a ? fd[e] : 0.f;
+      fd[e] = add ? g + fa[e] : g;
+    }
+    reinterpret_cast<uint4*>(dx)[i] = f_to_chunk(fd, (const T*)nullptr);
+  }
+  for (int64_t i = nc * CE + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float g = fabsf(to_f(x[i])) <= a ? to_f(dy[i]) : 0.f;
+    if (add) g += to_f(add[i]);
+    dx[i] = from_f<T>(g);
+  }
+}
+
 // ---- Quantization_int8 of a BatchNorm(+ReLU) output, the BatchNorm applied on load
 // (rn_quant_int8_fwd_codes_bn). Thread = one 16-channel group (one 16-byte code chunk) of the rows
 // r0 + tr, r0 + tr + rl, ...; y = [relu](fmaf(x, scale, shift)) rounded to T exactly as bn_apply_kernel
@@ -944,6 +1090,98 @@ __global__ __launch_bounds__(256) void wq_pack_kernel(const rn_wquant_item* __re
         it.qw[kt_ * cr + ci] = q * unit;
         if (it.w_codes) it.w_codes[kt_ * it.c + ci] = (int8_t)(int)q;
         tile[r][cl] = q * unit;
+      }
+    }
+    if (!out) continue;  // (uniform over the block)
+    __syncthreads();
+#pragma unroll 4
+    for (int j = 0; j < 16; ++j) {  // rows c, columns k: coalesced over k
+      const int r = r0 + 4 * j, ci = c0 + r, k = k0 + cl;
+      if (k < K && ci < cr) out[((int64_t)ci * RS + tap) * it.k_pad + k] = from_f<T>(tile[cl][r]);
+    }
+    __syncthreads();
+  }
+}
+
+// ---- batched GDRQ weight quantization (rn_weight_gdrq_pack): blockIdx.y = weight
+// sum |w| of each tensor: kWgdrqBlocks blocks per weight, each thread's elements in index order (16-byte chunks
+// where the master is aligned, then the tail), the wave butterfly, the four waves through LDS, one partial per
+// block at ws[weight * kWgdrqBlocks + block] -- no atomics
+constexpr int kWgdrqBlocks = 64;
+__global__ __launch_bounds__(256) void wgdrq_abssum_kernel(const rn_wgdrq_item* __restrict__ items,
+                                                           float* __restrict__ part) {
+  const rn_wgdrq_item it = items[blockIdx.y];
+  const int64_t n = (int64_t)it.k * it.rs * it.c_real;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  float s = 0.f;
+  int64_t i0 = 0;
+  if ((reinterpret_cast<uintptr_t>(it.master) & 15) == 0) {
+    const int64_t nc = n / 4;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nc; i += stride) {
+      const float4 v = reinterpret_cast<const float4*>(it.master)[i];
+      s += fabsf(v.x);
+      s += fabsf(v.y);
+      s += fabsf(v.z);
+      s += fabsf(v.w);
+    }
+    i0 = nc * 4;
+  }
+  for (int64_t i = i0 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride) s += fabsf(it.master[i]);
+  s = wave_sum(s);
+  __shared__ float wsum[4];
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) part[(int64_t)blockIdx.y * kWgdrqBlocks + blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+// one thread per weight: its partials added in block order, alpha := ktimes * (sum / count) unless fix_alpha
+// (each operation rounded to fp32 on its own), the unit; the threshold the pack reads is left at
+// ws[count * kWgdrqBlocks + weight]
+__global__ void wgdrq_state_kernel(const rn_wgdrq_item* __restrict__ items, int count, float* __restrict__ ws) {
+#pragma clang fp contract(off)
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= count) return;
+  const rn_wgdrq_item it = items[j];
+  float a = it.alpha[0];
+  if (!it.fix_alpha) {
+    float t = 0.f;
+#pragma unroll 16
+    for (int b = 0; b < kWgdrqBlocks; ++b) t += ws[(int64_t)j * kWgdrqBlocks + b];
+    a = it.ktimes * (t / (float)((int64_t)it.k * it.rs * it.c_real));
+    it.alpha[0] = a;
+  }
+  ws[(int64_t)count * kWgdrqBlocks + j] = a;
+  if (it.unit) it.unit[0] = a / (float)((1 << it.nbits) - 1);
+}
+// One read of the master per weight, in wq_pack_kernel's 64(k) x 64(c) tiles of one tap: each element's
+// q = round(clip(w, -alpha, alpha) / unit) computed once; the fake-quantized copy, the int8 codes and the forward
+// copy stored in master (KRSC) order, the data-gradient copy (CRSK) transposed through LDS
+template <typename T>
+__global__ __launch_bounds__(256) void wgdrq_pack_kernel(const rn_wgdrq_item* __restrict__ items, int count,
+                                                         const float* __restrict__ ws) {
+  __shared__ float tile[64][65];
+  const rn_wgdrq_item it = items[blockIdx.y];
+  const float a = ws[(int64_t)count * kWgdrqBlocks + blockIdx.y];
+  const float unit = a / (float)((1 << it.nbits) - 1);
+  const int RS = it.rs, cr = it.c_real, K = it.k;
+  const int kt = (K + 63) / 64, ct = (cr + 63) / 64;
+  const int ntiles = kt * RS * ct;
+  T* __restrict__ fwd = reinterpret_cast<T*>(it.w_krsc);
+  T* __restrict__ out = reinterpret_cast<T*>(it.w_crsk);
+  const int cl = threadIdx.x & 63, r0 = threadIdx.x >> 6;
+  for (int tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
+    const int c0 = (tl % ct) * 64, rest = tl / ct;
+    const int tap = rest % RS, k0 = (rest / RS) * 64;
+#pragma unroll 4
+    for (int j = 0; j < 16; ++j) {  // rows k0 + r, columns c0 + cl: coalesced over c
+      const int r = r0 + 4 * j, k = k0 + r, ci = c0 + cl;
+      if (k < K && ci < cr) {
+        const int64_t kt_ = (int64_t)k * RS + tap;
+        const float q = gdrq_code(it.master[kt_ * cr + ci], a, unit);
+        const float v = q * unit;
+        it.qw[kt_ * cr + ci] = v;
+        if (it.w_codes) it.w_codes[kt_ * it.c + ci] = (int8_t)(int)q;
+        if (fwd) fwd[kt_ * it.c + ci] = from_f<T>(v);
+        tile[r][cl] = v;
       }
     }
     if (!out) continue;  // (uniform over the block)
@@ -1660,6 +1898,84 @@ int rn_pact_bwd(int32_t dtype, int64_t n, const void* x, const void* dy, const f
                        (float*)dx, gamma, (const float*)add_src, (float*)ws);
   hipLaunchKernelGGL(pact_dgamma_kernel, dim3(1), dim3(64), 0, st, (const float*)ws, nblk, dgamma);
   return rn_check_launch("pact_bwd");
+}
+
+int64_t rn_gdrq_ws_bytes(int64_t n) { return n > 0 ? (int64_t)sizeof(float) * gdrq_sum_blocks(n) : 0; }
+
+int rn_gdrq_fwd(int32_t dtype, int64_t n, int64_t n_real, const void* x, float* alpha, int32_t nbits,
+                int32_t update, float ktimes, float lamda, void* out, void* codes, float* unit, void* ws,
+                rn_stream_t stream) {
+  RN_CHECK_ARG(x && alpha && n > 0 && (out || codes), "bad arguments");
+  RN_CHECK_ARG(dtype == RN_BF16 || dtype == RN_F32, "bad dtype");
+  RN_CHECK_ARG(nbits >= 1 && nbits <= 16, "bad nbits");
+  RN_CHECK_ARG(!codes || nbits <= 7, "int8 codes need nbits <= 7 (codes up to 2^nbits - 1 must fit a signed byte)");
+  RN_CHECK_ARG(!codes || n % 16 == 0, "int8 codes: n must be a multiple of 16");
+  RN_CHECK_ARG(!update || (ws && n_real > 0 && n_real <= n), "update needs the workspace and 0 < n_real <= n");
+  RN_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)codes & 15) == 0,
+               "16-byte aligned x / out / codes");
+  hipStream_t st = as_stream(stream);
+  const float levels = (float)((1 << nbits) - 1);
+  if (update) {
+    const int nblk = gdrq_sum_blocks(n);
+    if (dtype == RN_BF16)
+      hipLaunchKernelGGL(gdrq_abssum_kernel<bf16_t>, dim3(nblk), dim3(256), 0, st, n, (const bf16_t*)x, (float*)ws);
+    else
+      hipLaunchKernelGGL(gdrq_abssum_kernel<float>, dim3(nblk), dim3(256), 0, st, n, (const float*)x, (float*)ws);
+    hipLaunchKernelGGL(gdrq_alpha_kernel, dim3(1), dim3(64), 0, st, (const float*)ws, nblk, (float)n_real, ktimes,
+                       lamda, levels, alpha, unit);
+  }
+  if (codes) {
+    const int64_t nc = n / 16;
+    if (dtype == RN_BF16)
+      hipLaunchKernelGGL(gdrq_codes_kernel<bf16_t>, dim3(grid1d(nc)), dim3(256), 0, st, nc, (const bf16_t*)x,
+                         (bf16_t*)out, (int8_t*)codes, alpha, levels, unit);
+    else
+      hipLaunchKernelGGL(gdrq_codes_kernel<float>, dim3(grid1d(nc)), dim3(256), 0, st, nc, (const float*)x,
+                         (float*)out, (int8_t*)codes, alpha, levels, unit);
+  } else {
+    const int64_t nc = n / (dtype == RN_BF16 ? 8 : 4) + 1;
+    if (dtype == RN_BF16)
+      hipLaunchKernelGGL(gdrq_values_kernel<bf16_t>, dim3(grid1d(nc)), dim3(256), 0, st, n, (const bf16_t*)x,
+                         (bf16_t*)out, alpha, levels, unit);
+    else
+      hipLaunchKernelGGL(gdrq_values_kernel<float>, dim3(grid1d(nc)), dim3(256), 0, st, n, (const float*)x,
+                         (float*)out, alpha, levels, unit);
+  }
+  return rn_check_launch("gdrq_fwd");
+}
+
+int rn_gdrq_bwd(int32_t dtype, int64_t n, const void* x, const void* dy, const float* alpha, void* dx,
+                const void* add_src, rn_stream_t stream) {
+  RN_CHECK_ARG(x && dy && alpha && dx && n > 0, "bad arguments");
+  RN_CHECK_ARG(dtype == RN_BF16 || dtype == RN_F32, "bad dtype");
+  RN_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)dx & 15) == 0 &&
+                   ((uintptr_t)add_src & 15) == 0, "16-byte aligned x / dy / dx / add_src");
+  hipStream_t st = as_stream(stream);
+  const int64_t nc = n / (dtype == RN_BF16 ? 8 : 4) + 1;
+  if (dtype == RN_BF16)
+    hipLaunchKernelGGL(gdrq_bwd_kernel<bf16_t>, dim3(grid1d(nc)), dim3(256), 0, st, n, (const bf16_t*)x,
+                       (const bf16_t*)dy, (bf16_t*)dx, alpha, (const bf16_t*)add_src);
+  else
+    hipLaunchKernelGGL(gdrq_bwd_kernel<float>, dim3(grid1d(nc)), dim3(256), 0, st, n, (const float*)x,
+                       (const float*)dy, (float*)dx, alpha, (const float*)add_src);
+  return rn_check_launch("gdrq_bwd");
+}
+
+int64_t rn_weight_gdrq_ws_bytes(int32_t count) {
+  return count > 0 ? (int64_t)sizeof(float) * count * (kWgdrqBlocks + 1) : 0;
+}
+
+int rn_weight_gdrq_pack(const rn_wgdrq_item* items, int32_t count, int32_t dtype, float* ws, rn_stream_t stream) {
+  RN_CHECK_ARG(items && ws && count > 0 && count <= 65535, "bad arguments");
+  RN_CHECK_ARG(dtype == RN_BF16 || dtype == RN_F32, "bad dtype");
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(wgdrq_abssum_kernel, dim3(kWgdrqBlocks, count), dim3(256), 0, st, items, ws);
+  hipLaunchKernelGGL(wgdrq_state_kernel, dim3((count + 63) / 64), dim3(64), 0, st, items, count, ws);
+  if (dtype == RN_BF16)
+    hipLaunchKernelGGL(wgdrq_pack_kernel<bf16_t>, dim3(256, count), dim3(256), 0, st, items, count, ws);
+  else
+    hipLaunchKernelGGL(wgdrq_pack_kernel<float>, dim3(256, count), dim3(256), 0, st, items, count, ws);
+  return rn_check_launch("weight_gdrq_pack");
 }
 
 }  // extern "C"

@@ -3,10 +3,11 @@
 The reference registers Python CustomOps at import time (symbol/clip_grad_quantization_int8.py:70,
 symbol/quant_ops.py:44, core/operator/*.py), so the classes must exist for `from symbol import *`
 to succeed. Executing a Python CustomOp inside the MI355X plan is not supported: this module stays a
-registration surface. mx.sym.Custom asks the prop registered under its op_type for list_arguments() and
-infer_shape() only (symbol.py), so that Custom(data=, gamma=, nbits="4", op_type="PACT_PY") gets its gamma input;
-a PACT_PY node lowers to the runtime's own PACT kernels (rn/executor.py), and a graph with any other Custom
-op_type fails at bind with an error that names it. forward / backward of a CustomOp are never called.
+registration surface. mx.sym.Custom asks the prop registered under its op_type for list_arguments(),
+list_auxiliary_states() and infer_shape() only (symbol.py), so that Custom(data=, gamma=, nbits="4",
+op_type="PACT_PY") gets its gamma input and Custom(data=, alpha=, op_type="GDRQ_PY") its auxiliary alpha;
+a PACT_PY / GDRQ_PY node lowers to the runtime's own PACT / GDRQ kernels (rn/executor.py), and a graph with any
+other Custom op_type fails at bind with an error that names it. forward / backward of a CustomOp are never called.
 """
 
 _REGISTRY = {}

@@ -115,6 +115,9 @@ _reg(OpSpec("_contrib_BroadcastScale", ["data", "scaler"], hint="broadcastscale"
 # the fork's PACT: activation quantization with a learned clipping threshold gamma (1,)
 # (core/graph_optimize.py:184-187)
 _reg(OpSpec("_contrib_PACT", ["data", "gamma"], hint="pact"))
+# the fork's GDRQ: quantization with a mean-based clipping threshold; alpha (1,) is an auxiliary state
+# (core/graph_optimize.py:192-195)
+_reg(OpSpec("_contrib_GDRQ", ["data"], ["alpha"], hint="gdrq"))
 
 
 def _custom_prop(node):
@@ -406,6 +409,13 @@ def _infer_node(n, shapes, partial):
     elif op == "_contrib_PACT":
         _set(shapes, ins[1], (1,))
         _set(shapes, (n, 0), dshape)
+    elif op == "_contrib_GDRQ":
+        gs = int(_parse(n.attrs.get("group_size", -1)))
+        if gs == -1:
+            _set(shapes, ins[1], (1,))
+        else:  # (one threshold per channel group: core/operator/GDRQ.py:171-183; refused at bind)
+            _set(shapes, ins[1], (dshape[0 if _parse(n.attrs.get("is_weight", False)) else 1] // gs,))
+        _set(shapes, (n, 0), dshape)
     elif op == "Custom" and _custom_prop(n) is not None:
         # the registered prop's infer_shape: ([input shapes], [output shapes], [aux shapes]); an input
         # whose shape is not known yet is passed empty, as MXNet passes it
@@ -587,6 +597,7 @@ class _Contrib:
     Quantization_int8 = staticmethod(_make("_contrib_Quantization_int8"))
     BroadcastScale = staticmethod(_make("_contrib_BroadcastScale"))
     PACT = staticmethod(_make("_contrib_PACT"))
+    GDRQ = staticmethod(_make("_contrib_GDRQ"))
 
     def __getattr__(self, item):
         raise MXNetError("contrib operator %s is not provided by this runtime" % item)

@@ -6,7 +6,8 @@ gpu_list=[] meaning no GPU). A Module bound to mx.cpu() contexts runs here: ever
 (rn/executor.py) as a torch-CPU fp32 operator (oneDNN, the analogue of MXNet's MKL-DNN CPU path),
 with MXNet's semantics -- BatchNorm batch statistics with biased variance and momentum moving stats,
 fix_gamma / use_global_stats, SoftmaxOutput's p - onehot gradient, Quantization_int8 with EMA
-thresholds and the clipped STE, PACT with its learned threshold, MXNet momentum SGD with wd_mult 0 on
+thresholds and the clipped STE, PACT with its learned threshold, GDRQ with its mean-based threshold,
+MXNet momentum SGD with wd_mult 0 on
 biases / betas -- and the same
 flat fp32 parameter / gradient / momentum / aux buffers the GPU executor has, so Module,
 kvstore (gloo all-reduce over the flat gradient), checkpoints and metrics work unchanged.
@@ -47,8 +48,9 @@ class CPUExecutor:
         self._q = _QuantState()
         # the last forward's discrete decisions, kept for parity tests that replay them in a higher precision (on
         # the GPU they sit in device buffers): ReLU masks by Activation name, fake-quantized weights by quantizer
-        # name, PACT codes / x < gamma masks / units by gamma name
-        self.decisions = {"relu": {}, "wq": {}, "pact": {}}
+        # name, PACT codes / x < gamma masks / units by gamma name, GDRQ codes / |x| <= alpha masks / alphas / units
+        # by alpha name (weights and activations)
+        self.decisions = {"relu": {}, "wq": {}, "pact": {}, "gdrq": {}}
         self._out = {}
         self._head = None
         self.num_update = 0
@@ -211,6 +213,9 @@ class CPUExecutor:
                 env[id(op.y)] = self._quant_act(get(op.x), op.q, train)
             elif k == "pact":
                 env[id(op.y)] = self._pact(op.gamma, get(op.x), P(op.gamma), op.nbits)
+            elif k == "gdrq":
+                env[id(op.y)] = self._gdrq(get(op.x), op.alpha, op.nbits, op.fix_alpha, op.ktimes, op.lamda, False,
+                                           train)
             elif k == "add":
                 y = get(op.a) + get(op.b)
                 env[id(op.y)] = F.relu(y) if op.relu else y
@@ -303,10 +308,44 @@ class CPUExecutor:
             self.decisions["pact"][name] = {"codes": q, "mask": x.detach() < g.detach(), "unit": float(unit)}
         return v + (c - c.detach())  # (exactly v; the gradient is the where's)
 
+    def _gdrq(self, x, alpha_name, nbits, fix_alpha, ktimes, lamda, is_weight, train):
+        """GDRQ, per-tensor form (core/operator/GDRQ.py:64-86,124-133), in fp32: unless fix_alpha, thr = ktimes *
+        mean|x| and alpha := thr (weights: a pure function of the weight, recomputed in every forward) or alpha +=
+        lamda * (alpha - thr) (activations, the reference's sign; training forwards only -- inference reads alpha);
+        then clip to +-alpha and round half away from zero to the grid unit = alpha / (2^nbits - 1). Backward:
+        straight-through for weights, dy * [|x| <= alpha] for activations. The last forward's codes, mask, alpha
+        and unit stay in self.decisions["gdrq"][alpha_name]."""
+        al = self._auxv(alpha_name)
+        with torch.no_grad():
+            xd = x.detach()
+            if not fix_alpha and (is_weight or train):
+                thr = torch.tensor(ktimes, dtype=torch.float32) * (xd.abs().sum() / float(xd.numel()))
+                if is_weight:
+                    al.fill_(float(thr))
+                else:
+                    al.copy_(al + torch.tensor(lamda, dtype=torch.float32) * (al - thr))
+            a = al[0].clone()
+            unit = a / float(2 ** nbits - 1)
+            if float(unit) > 0:
+                r = torch.minimum(torch.maximum(xd, -a), a) / unit
+                t = torch.trunc(r)  # (r - t is exact: roundf, without floor(|r| + 0.5)'s double rounding)
+                q = t + torch.sign(r) * ((r - t).abs() >= 0.5).to(r.dtype)
+            else:
+                q = torch.zeros_like(xd)
+            v = q * unit
+            mask = torch.ones_like(xd, dtype=torch.bool) if is_weight else xd.abs() <= a
+            self.decisions["gdrq"][alpha_name] = {"codes": q, "mask": mask, "alpha": float(a), "unit": float(unit)}
+        xm = x if is_weight else x * mask.to(x.dtype)
+        return v + (xm - xm.detach())  # (exactly v; the gradient is the mask's)
+
     def _weight(self, w, qw, train):
         """Quantization_int8 on a weight (per tensor, no clip, plain STE: symbol/quant_ops.py:17-31)."""
         if qw is None:
             return w
+        if qw.get("family") == "gdrq":
+            v = self._gdrq(w, qw["alpha"], qw["nbits"], qw["fix_alpha"], qw["ktimes"], 0.0, True, train)
+            self.decisions["wq"][qw["name"]] = v.detach()
+            return v
         t = self._qthreshold(w, qw, train, True)
         unit = t / float(2 ** (qw["nbits"] - 1) - 1)
         with torch.no_grad():

@@ -102,6 +102,8 @@ class Plan:
         self.alias = {}
         self.ops = []
         self.qweight = {}  # id(weight Quantization_int8 node) -> quant info
+        self.qweight_gdrq = {}  # id(weight GDRQ node) -> quant info (family "gdrq")
+        self._gdrq_alphas = {}  # alpha variable -> the GDRQ node that owns it
         self._lower()
 
     # --- shapes of every node output
@@ -264,6 +266,9 @@ class Plan:
                     y = self._new_tensor(n, x.shape)
                     self.ops.append(PlanOp("quant", n.name, x=x, y=y, q=q))
                 done.add(id(n))
+            elif self._is_gdrq(n):
+                self._lower_gdrq(n)
+                done.add(id(n))
             elif op == "_contrib_PACT" or op == "Custom":
                 self._lower_pact(n)
                 done.add(id(n))
@@ -336,6 +341,55 @@ class Plan:
         y = self._new_tensor(n, x.shape)
         self.ops.append(PlanOp("pact", n.name, x=x, y=y, gamma=g.name, nbits=nbits))
 
+    @staticmethod
+    def _is_gdrq(node):
+        return node is not None and (node.op == "_contrib_GDRQ" or
+                                     (node.op == "Custom" and _parse(node.attrs.get("op_type")) == "GDRQ_PY"))
+
+    def _lower_gdrq(self, n):
+        """GDRQ (core/graph_optimize.py:188-195): mx.sym.contrib.GDRQ or mx.sym.Custom(op_type="GDRQ_PY"), per-tensor
+        form -- out = round(clip(x, -alpha, alpha) / unit) * unit, unit = alpha / (2^nbits - 1), a symmetric signed
+        code for weights and activations alike (core/operator/GDRQ.py:50-190; attribute defaults as GDRQ_PYProp).
+        alpha is an auxiliary state of shape (1,), no parameter: with fix_alpha it keeps the value it was
+        initialised or loaded with; otherwise thr = ktimes * mean|x| moves it before the clip -- a weight's alpha is
+        set to thr, an activation's becomes alpha + lamda * (alpha - thr) in training forwards (the reference's sign).
+        A weight quantizer becomes a record on its convolution (self.qweight_gdrq, straight-through backward); an
+        activation quantizer a "gdrq" op. The Python forward / backward of the CustomOp are never run."""
+        a = n.attrs
+        if int(_parse(a.get("group_size", -1))) != -1:
+            raise PlanError("%s: GDRQ group_size %s not supported (per-tensor thresholds only, group_size=-1)"
+                            % (n.name, a.get("group_size")))
+        if int(_parse(a.get("delay_quant", 0))):
+            raise PlanError("%s: GDRQ delay_quant > 0 not supported" % n.name)
+        if len(n.inputs) != 2:
+            raise PlanError("%s: GDRQ takes data and the auxiliary state alpha" % n.name)
+        av = n.inputs[1][0]
+        if av.op != "null" or av.name in self.input_shapes:
+            raise PlanError("%s: GDRQ's alpha must be an auxiliary state Variable" % n.name)
+        if av.name in self._gdrq_alphas:
+            raise PlanError("%s: alpha %s is shared with GDRQ node %s (not supported)"
+                            % (n.name, av.name, self._gdrq_alphas[av.name]))
+        self._gdrq_alphas[av.name] = n.name
+        nbits = int(_parse(a.get("nbits", 4)))
+        if not 1 <= nbits <= 16:
+            raise PlanError("%s: GDRQ nbits %d not supported" % (n.name, nbits))
+        q = dict(family="gdrq", name=n.name, alpha=av.name, nbits=nbits,
+                 fix_alpha=bool(_parse(a.get("fix_alpha", False))), ktimes=float(_parse(a.get("ktimes", 3))),
+                 lamda=float(_parse(a.get("lamda", 0.001))), is_weight=bool(_parse(a.get("is_weight", False))))
+        src = n.inputs[0][0]
+        if q["is_weight"]:
+            if src.op != "null":
+                raise PlanError("%s: weight quantization of a computed tensor" % n.name)
+            q["param"] = src.name
+            self.qweight_gdrq[id(n)] = q
+            return
+        x = self.tensor(src)
+        if x.kind != "act":
+            raise PlanError("%s: GDRQ of a non-activation tensor" % n.name)
+        y = self._new_tensor(n, x.shape)
+        self.ops.append(PlanOp("gdrq", n.name, x=x, y=y, alpha=av.name, nbits=nbits, fix_alpha=q["fix_alpha"],
+                               ktimes=q["ktimes"], lamda=q["lamda"]))
+
     def _nonneg(self, t):
         """Is activation tensor `t` known to be >= 0: written by a BatchNorm with fused ReLU, a relu op, an add
         with ReLU, or a pooling of one of those (PACT has no lower clip: only then are its codes 0 .. 2^nbits - 1)?"""
@@ -352,24 +406,31 @@ class Plan:
         int8 MFMAs (rn_conv_fwd_i8): exact integer sums of the codes, scaled by the two units, instead
         of bf16 / fp32 products of the fake-quantized values. RN_INT8_MFMA=0: the fake-quant path.
         A PACT input quantizer qualifies with nbits <= 7 (its codes reach 2^nbits - 1) over a tensor known to be
-        non-negative (_nonneg); otherwise its convolution multiplies the fake-quantized values."""
-        producer = {id(op.y): op for op in self.ops if op.kind in ("quant", "pact")}
+        non-negative (_nonneg); otherwise its convolution multiplies the fake-quantized values. A GDRQ quantizer's
+        codes are signed, -L .. L with L = 2^nbits - 1: it qualifies with nbits <= 7 on the data side whatever its
+        input's sign, and on the weight side (Quantization_int8 weights: nbits <= 8); mixed pairs qualify side by
+        side."""
+        producer = {id(op.y): op for op in self.ops if op.kind in ("quant", "pact", "gdrq")}
         on = os.environ.get("RN_INT8_MFMA", "1") != "0"
         for op in self.ops:
-            if op.kind in ("quant", "pact"):
+            if op.kind in ("quant", "pact", "gdrq"):
                 op.emit_codes = False
-            if op.kind == "pact":
-                op.codes_wgrad = False  # (never for PACT: the values are always written)
+            if op.kind in ("pact", "gdrq"):
+                op.codes_wgrad = False  # (never for PACT / GDRQ: the values are always written)
         for op in self.ops:
             if op.kind != "conv":
                 continue
             q = producer.get(id(op.x))
             if q is not None and q.kind == "pact":
                 q_ok = q.nbits <= 7 and self._nonneg(q.x)
+            elif q is not None and q.kind == "gdrq":
+                q_ok = q.nbits <= 7  # (signed codes -L .. L, L = 2^nbits - 1 <= 127; the input's sign is free)
             else:
                 q_ok = q is not None and q.q["nbits"] <= 8
-            op.int8 = bool(on and op.qweight is not None and q_ok and op.groups == 1 and
-                           op.x.cp % 16 == 0 and op.qweight["nbits"] <= 8 and
+            # (a GDRQ weight's codes reach 2^nbits - 1, a Quantization_int8 weight's 2^(nbits - 1) - 1)
+            w_ok = op.qweight is not None and \
+                op.qweight["nbits"] <= (7 if op.qweight.get("family") == "gdrq" else 8)
+            op.int8 = bool(on and w_ok and q_ok and op.groups == 1 and op.x.cp % 16 == 0 and
                            getattr(op, "xf", None) is None)
             op.qsrc = q if op.int8 else None
             if op.int8:
@@ -465,13 +526,15 @@ class Plan:
         p = node.inputs[idx][0]
         if self._is_quant(p) and id(p) in self.qweight:
             return self.qweight[id(p)]["param"]
+        if id(p) in self.qweight_gdrq:
+            return self.qweight_gdrq[id(p)]["param"]
         if p.op != "null":
             raise PlanError("%s: computed weights are not supported" % node.name)
         return p.name
 
     def _weight_quant(self, node, idx=1):
         p = node.inputs[idx][0]
-        return self.qweight.get(id(p)) if self._is_quant(p) else None
+        return self.qweight.get(id(p)) if self._is_quant(p) else self.qweight_gdrq.get(id(p))
 
     def _conv_attrs(self, n):
         k = _tup(n.attrs["kernel"])
@@ -999,6 +1062,8 @@ class Executor:
         # every weight quantizer in one rn_weight_quant_pack (RN_WQUANT_BATCH=0: three calls per weight)
         self._wq_batch = os.environ.get("RN_WQUANT_BATCH", "1") == "1"
         self._wq_ops = []
+        self._wg_ops = []  # the ops with a GDRQ weight: one rn_weight_gdrq_pack for all of them
+        self._gdrq_ws = None  # rn_gdrq_fwd's block partials: one buffer for every updating GDRQ (compute stream)
         self.fused_packs = {}  # param -> rn_wpack fields: copies rewritten by the SGD kernel itself
         self.unfused_packs = []  # packs that still run after every update (grouped, fake-quantized)
         # the grouped layers' repacks in one rn_conv_weight_pack_multi (RN_GPACK_BATCH=0: one call each)
@@ -1166,13 +1231,17 @@ class Executor:
                 assert (d.p, d.q) == (y.h, y.w), (op.name, d.p, d.q, y.h, y.w)
                 op.desc = d
                 op.wc = self._zeros(self.lib.rn_conv_pack_numel(L.C.byref(d), 1), self.tdtype)
-                if getattr(op, "int8", False):
+                wgdrq = op in self._wg_ops
+                if wgdrq and op.groups == 1 and not getattr(op, "int8", False):
+                    # (both compute copies written by rn_weight_gdrq_pack; their padding stays zero)
+                    op.wk = self._zeros(self.lib.rn_conv_pack_numel(L.C.byref(d), 0), self.tdtype)
+                elif getattr(op, "int8", False):
                     # forward copy: the int8 codes (KRSC); the data-gradient copy stays the
                     # fake-quantized values in the compute dtype (STE backward)
                     op.wk = None
                     op.wk8 = self.torch.zeros(int(self.lib.rn_conv_pack_numel(L.C.byref(d), 0)),
                                               dtype=self.torch.int8, device=self.device)
-                    if not self._wq_batch:  # (batched: written by rn_weight_quant_pack)
+                    if not self._wq_batch and not wgdrq:  # (batched: written by rn_weight_quant_pack)
                         self._add_pack(op, d, None, op.wc, sp)
                         c_ = self._call("rn_conv_weight_pack_i8", L.C.byref(d), self._pp(op.weight),
                                         self._p(op.wunit), self._p(op.wk8), sp)
@@ -1283,6 +1352,22 @@ class Executor:
                                op.nbits, self._p(self.act(op.y)), self._p(op.codes), self._p(op.unit), sp)
                 F.append(c)
                 I.append(c)
+            elif op.kind == "gdrq":
+                # alpha is read (and, in training without fix_alpha, first updated) on the device in the aux buffer:
+                # no host synchronisation, a replayed graph sees the current value. Inference never writes it. The
+                # values are always written; with emit_codes also the signed int8 codes and the unit
+                x = op.x
+                op.unit = self._zeros(1, self.torch.float32)
+                op.codes = self.torch.zeros(x.numel, dtype=self.torch.int8, device=self.device) \
+                    if op.emit_codes else None
+                if not op.fix_alpha and self._gdrq_ws is None:
+                    nmax = max(o.x.numel for o in plan.ops if o.kind == "gdrq" and not o.fix_alpha)
+                    self._gdrq_ws = self._zeros(int(self.lib.rn_gdrq_ws_bytes(nmax)) // 4, self.torch.float32)
+                for lst, upd in ((F, int(not op.fix_alpha)), (I, 0)):
+                    lst.append(self._call("rn_gdrq_fwd", self.dtype, x.numel, x.rows * x.c, self._p(self.act(x)),
+                                          self._ap(op.alpha), op.nbits, upd, op.ktimes, op.lamda,
+                                          self._p(self.act(op.y)), self._p(op.codes), self._p(op.unit),
+                                          self._p(self._gdrq_ws) if upd else None, sp))
             elif op.kind == "add" and getattr(op, "bn_a", None) is not None:
                 bna, bnb = op.bn_a, op.bn_b
                 other = op.b if op.bn_a_key == "a" else op.a
@@ -1322,7 +1407,8 @@ class Executor:
                 op.desc = d
                 op.wk = self._zeros(op.nh * x.cp, self.tdtype)
                 op.wc = self._zeros(x.cp * _pad8(op.nh), self.tdtype)
-                self._add_pack(op, d, op.wk, op.wc, sp)
+                if op not in self._wg_ops:  # (a GDRQ weight: both copies written by rn_weight_gdrq_pack)
+                    self._add_pack(op, d, op.wk, op.wc, sp)
                 bias = self._pp(op.bias) if op.bias else None
                 c = self._call("rn_conv_fwd", L.C.byref(d), self._p(self.act(x)), self._p(op.wk),
                                self._p(self.act(y)), F32, None, bias, sp)
@@ -1359,6 +1445,34 @@ class Executor:
             arr = (L.WQuantItem * len(items))(*items)
             self._wq_items = self.torch.frombuffer(bytearray(arr), dtype=self.torch.uint8).to(self.device)
             c_ = self._call("rn_weight_quant_pack", self._p(self._wq_items), len(items), self.dtype, qwsp, sp)
+            self.packs.insert(0, c_)
+            self.unfused_packs.insert(0, c_)
+        if self._wg_ops:
+            # every GDRQ weight in one rn_weight_gdrq_pack, ahead of the packs that read its fake-quantized copies
+            # (the stem's and the grouped layers'): thresholds, units, the copies of the dense layers
+            items = []
+            for op in self._wg_ops:
+                shape = self.plan.param_shape(op.weight)
+                k, creal = shape[0], shape[1]
+                rs = int(np.prod(shape[2:])) if len(shape) > 2 else 1
+                i8 = getattr(op, "int8", False)
+                dense = op.kind == "fc" or (op.kind == "conv" and op.groups == 1)
+                d = op.desc if dense else None
+                assert not dense or (d.k == k and d.c_real == creal and d.r * d.s == rs), op.name
+                q = op.qweight
+                items.append(L.WGdrqItem(
+                    master=self._pp(op.weight).value, qw=op.qw.data_ptr(),
+                    unit=op.wunit.data_ptr() if i8 else None, alpha=self._ap(q["alpha"]).value,
+                    w_codes=op.wk8.data_ptr() if i8 else None,
+                    w_krsc=op.wk.data_ptr() if dense and not i8 else None,
+                    w_crsk=op.wc.data_ptr() if dense else None,
+                    k=k, rs=rs, c_real=creal, c=d.c if dense else creal, k_pad=d.k_pad if dense else k,
+                    nbits=int(q["nbits"]), fix_alpha=int(q["fix_alpha"]), ktimes=float(q["ktimes"])))
+            arr = (L.WGdrqItem * len(items))(*items)
+            self._wg_items = self.torch.frombuffer(bytearray(arr), dtype=self.torch.uint8).to(self.device)
+            self._wg_ws = self._zeros(int(self.lib.rn_weight_gdrq_ws_bytes(len(items))) // 4, self.torch.float32)
+            c_ = self._call("rn_weight_gdrq_pack", self._p(self._wg_items), len(items), self.dtype,
+                            self._p(self._wg_ws), sp)
             self.packs.insert(0, c_)
             self.unfused_packs.insert(0, c_)
         if self._gpacks:
@@ -1478,6 +1592,11 @@ class Executor:
         op.qw = self._zeros(n, self.torch.float32)
         if getattr(op, "int8", False):  # also keeps the unit for the int8 codes of the forward copy
             op.wunit = self._zeros(1, self.torch.float32)
+        if q.get("family") == "gdrq":
+            # a GDRQ weight (core/operator/GDRQ.py: alpha = ktimes * mean|w| unless fix_alpha, clip, round; plain
+            # STE): always through the batched rn_weight_gdrq_pack, built after the forward
+            self._wg_ops.append(op)
+            return self._p(op.qw)
         if self._wq_batch:
             # one batched rn_weight_quant_pack for every weight quantizer (built after the forward):
             # the fake-quantized copy, and for the int8 convs their codes and data-gradient copy too
@@ -1894,6 +2013,15 @@ class Executor:
                                             self._p(dy), self._pp(op.gamma), self._p(out), self._p(add),
                                             self._gp(op.gamma), self._p(self._pact_ws), sp))
                 self.param_done_at[op.gamma] = len(self._bwd)
+            elif op.kind == "gdrq":
+                # dx = dy * [|x| <= alpha], the boundary included (rn_gdrq_bwd; the BatchNorm-folded clip and
+                # rn_quant_int8_bwd exclude it), with the alpha the forward left. alpha has no gradient. As for
+                # PACT this call is the last writer of x's gradient and fuses no BatchNorm reduction
+                if op.x.needs_grad:
+                    out, add = gs.contribute(op.x)
+                    self._gw[id(op.x)] = ("other",)
+                    self._bwd.append(self._call("rn_gdrq_bwd", self.dtype, op.x.numel, self._p(self.act(op.x)),
+                                                self._p(dy), self._ap(op.alpha), self._p(out), self._p(add), sp))
             elif op.kind == "relu":
                 if op.x.needs_grad:
                     out, add = gs.contribute(op.x)

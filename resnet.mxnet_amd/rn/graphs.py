@@ -9,6 +9,8 @@ the reference function it mirrors, so checkpoints and parity fixtures are interc
   resnet_int8(...)     <-> symbol/resnet_int8.py:69-131 + int8_api.py:120-171 (fake-quant QAT)
   resnet50_pact(...)   <-> the same structure with the activation quantizers of core/graph_optimize.py:184-187
                            (PACT, learned clipping threshold) instead of Quantization_int8
+  resnet50_gdrq(...)   <-> the same structure with the GDRQ quantizers of core/graph_optimize.py:192-195 (mean-based
+                           clipping thresholds, symmetric signed codes) on weights and activations
   mobilenet(...)       <-> symbol/mobilenet.py:38-144    (MobileNet-v1: depthwise 3x3 + pointwise 1x1)
 The equivalence is checked against parameter counts and names restated from the reference
 (tests/test_symbol_plan.py) -- the reference files themselves are never imported.
@@ -156,21 +158,44 @@ def _pact(name, data, abits, pact_init):
     return mx.sym.contrib.PACT(data=data, gamma=gamma, name=name, **_nbits(abits))
 
 
+# the GDRQ setting of config/quant_attrs.py: weights follow ktimes * mean|w| (alpha starts at 0.5 and is overwritten
+# by the first forward), activations clip at a fixed alpha of 1.0
+GDRQ_WEIGHT = dict(fix_alpha=False, ktimes=3, init=0.5)
+GDRQ_ACT = dict(fix_alpha=True, init=1.0)
+
+
+def _gdrq(name, data, bits, is_weight, setting):
+    """create_quant_node's GDRQ_CXX branch (core/graph_optimize.py:192-195): the threshold '<name>_alpha', shape
+    (1,), an auxiliary state initialised to setting["init"]; the other entries are the operator's attributes."""
+    kw = dict(GDRQ_WEIGHT if is_weight else GDRQ_ACT)
+    kw.update(setting or {})
+    alpha = mx.sym.Variable(name=name + "_alpha", init=mx.init.Constant(kw.pop("init")), dtype="float32")
+    return mx.sym.contrib.GDRQ(data=data, alpha=alpha, name=name, is_weight=is_weight, **_nbits(bits), **kw)
+
+
 def quant_conv(name, data, num_filter, kernel, stride, pad=(0, 0), no_bias=True, num_group=1, in_channels=None,
                quant_mode="minmax", delay_quant=0, ema_decay=0.99, workspace=512, act_op="Quantization_int8",
-               wbits=None, abits=None, pact_init=8.0):
+               wbits=None, abits=None, pact_init=8.0, weight_op="Quantization_int8", gdrq_weight=None,
+               gdrq_act=None):
     """int8_api.py:120-150 quant_conv_cxx: Quantization_int8 on the weight ('<name>_weight') and on
     the data ('<name>_data') feeding a plain Convolution. act_op="PACT": the data quantizer is
-    mx.sym.contrib.PACT with `abits` bits instead."""
-    assert act_op in ("Quantization_int8", "PACT"), act_op
+    mx.sym.contrib.PACT with `abits` bits instead. act_op / weight_op "GDRQ": mx.sym.contrib.GDRQ with `abits` /
+    `wbits` bits and the attributes of `gdrq_act` / `gdrq_weight` over GDRQ_ACT / GDRQ_WEIGHT."""
+    assert act_op in ("Quantization_int8", "PACT", "GDRQ"), act_op
+    assert weight_op in ("Quantization_int8", "GDRQ"), weight_op
     weight = mx.sym.Variable(name=name + "_weight", shape=(num_filter, in_channels // num_group) + tuple(kernel),
                              dtype="float32")
-    weight_q = mx.sym.contrib.Quantization_int8(data=weight, name=name + "_weight", quant_mode=quant_mode,
-                                                is_weight=True, is_weight_perchannel=False, ema_decay=ema_decay,
-                                                delay_quant=delay_quant, grad_mode="ste", workspace=workspace,
-                                                **_nbits(wbits))
+    if weight_op == "GDRQ":
+        weight_q = _gdrq(name + "_weight", weight, wbits, True, gdrq_weight)
+    else:
+        weight_q = mx.sym.contrib.Quantization_int8(data=weight, name=name + "_weight", quant_mode=quant_mode,
+                                                    is_weight=True, is_weight_perchannel=False, ema_decay=ema_decay,
+                                                    delay_quant=delay_quant, grad_mode="ste", workspace=workspace,
+                                                    **_nbits(wbits))
     if act_op == "PACT":
         data_q = _pact(name + "_data", data, abits, pact_init)
+    elif act_op == "GDRQ":
+        data_q = _gdrq(name + "_data", data, abits, False, gdrq_act)
     else:
         data_q = mx.sym.contrib.Quantization_int8(data=data, name=name + "_data", quant_mode=quant_mode,
                                                   is_weight=False, is_weight_perchannel=False, ema_decay=ema_decay,
@@ -184,16 +209,23 @@ def quant_conv(name, data, num_filter, kernel, stride, pad=(0, 0), no_bias=True,
 
 
 def quant_fc(name, data, num_hidden, in_channels, quant_mode="minmax", delay_quant=0, ema_decay=0.99,
-             workspace=512, act_op="Quantization_int8", wbits=None, abits=None, pact_init=8.0):
-    """int8_api.py:152-171 quant_fc_cxx (act_op="PACT": as quant_conv)."""
-    assert act_op in ("Quantization_int8", "PACT"), act_op
+             workspace=512, act_op="Quantization_int8", wbits=None, abits=None, pact_init=8.0,
+             weight_op="Quantization_int8", gdrq_weight=None, gdrq_act=None):
+    """int8_api.py:152-171 quant_fc_cxx (act_op="PACT" / "GDRQ", weight_op="GDRQ": as quant_conv)."""
+    assert act_op in ("Quantization_int8", "PACT", "GDRQ"), act_op
+    assert weight_op in ("Quantization_int8", "GDRQ"), weight_op
     weight = mx.sym.Variable(name=name + "_weight", shape=(num_hidden, in_channels), dtype="float32")
-    fc_q = mx.sym.contrib.Quantization_int8(data=weight, name=name + "_weight", is_weight=True, ema_decay=ema_decay,
-                                            delay_quant=delay_quant, quant_mode=quant_mode,
-                                            is_weight_perchannel=False, grad_mode="ste", workspace=workspace,
-                                            **_nbits(wbits))
+    if weight_op == "GDRQ":
+        fc_q = _gdrq(name + "_weight", weight, wbits, True, gdrq_weight)
+    else:
+        fc_q = mx.sym.contrib.Quantization_int8(data=weight, name=name + "_weight", is_weight=True,
+                                                ema_decay=ema_decay, delay_quant=delay_quant, quant_mode=quant_mode,
+                                                is_weight_perchannel=False, grad_mode="ste", workspace=workspace,
+                                                **_nbits(wbits))
     if act_op == "PACT":
         data_q = _pact(name + "_data", data, abits, pact_init)
+    elif act_op == "GDRQ":
+        data_q = _gdrq(name + "_data", data, abits, False, gdrq_act)
     else:
         data_q = mx.sym.contrib.Quantization_int8(data=data, name=name + "_data", is_weight=False,
                                                   ema_decay=ema_decay, delay_quant=delay_quant, quant_mode=quant_mode,
@@ -221,16 +253,23 @@ def _int8_unit(x, cin, nf, stride, dim_match, name, bottle_neck, mom, qkw):
 
 def resnet_int8(units, num_stage, filter_list, num_classes, data_type="float32", bottle_neck=True, bn_mom=0.9,
                 workspace=512, memonger=False, grad_scale=1.0, dataset_type="imagenet", quant_mode="minmax",
-                delay_quant=0, ema_decay=0.99, act_op="Quantization_int8", wbits=None, abits=None, pact_init=8.0):
+                delay_quant=0, ema_decay=0.99, act_op="Quantization_int8", wbits=None, abits=None, pact_init=8.0,
+                weight_op="Quantization_int8", gdrq_weight=None, gdrq_act=None):
     """symbol/resnet_int8.py:69-131 (the C5 config graph; BN stays separate). act_op="PACT": every
     activation quantizer that reads a ReLU output -- all but conv0's, which stays Quantization_int8 on the
-    normalised image -- is mx.sym.contrib.PACT with `abits` bits; the weights stay Quantization_int8 (`wbits`)."""
+    normalised image -- is mx.sym.contrib.PACT with `abits` bits; the weights stay Quantization_int8 (`wbits`).
+    act_op="GDRQ": those quantizers are mx.sym.contrib.GDRQ; weight_op="GDRQ": so is every weight quantizer but
+    conv0's, which stays Quantization_int8 at its default 8 bits beside its data quantizer."""
     assert len(units) == num_stage
     qkw0 = dict(quant_mode=quant_mode, delay_quant=delay_quant, ema_decay=ema_decay, workspace=workspace)
     qkw = dict(qkw0)
-    if wbits is not None:
+    if weight_op != "Quantization_int8":
+        qkw.update(weight_op=weight_op, wbits=wbits, gdrq_weight=gdrq_weight)
+    elif wbits is not None:
         qkw0["wbits"] = qkw["wbits"] = wbits
-    if act_op != "Quantization_int8":
+    if act_op == "GDRQ":
+        qkw.update(act_op=act_op, abits=abits, gdrq_act=gdrq_act)
+    elif act_op != "Quantization_int8":
         qkw.update(act_op=act_op, abits=abits, pact_init=pact_init)
     elif abits is not None:
         qkw0["abits"] = qkw["abits"] = abits
@@ -311,6 +350,13 @@ def resnet50_pact(num_classes=1000, wbits=8, abits=4):
     and Quantization_int8 weights."""
     return resnet_int8([3, 4, 6, 3], 4, [64, 256, 512, 1024, 2048], num_classes, "float32", True, act_op="PACT",
                        wbits=wbits, abits=abits, pact_init=8.0)
+
+
+def resnet50_gdrq(num_classes=1000, wbits=4, abits=4):
+    """ResNet-50 with GDRQ quantizers in the reference's setting (config/quant_attrs.py): 4-bit weights whose
+    threshold follows 3 * mean|w| (alpha starting at 0.5), 4-bit activations clipped at a fixed alpha of 1.0."""
+    return resnet_int8([3, 4, 6, 3], 4, [64, 256, 512, 1024, 2048], num_classes, "float32", True, act_op="GDRQ",
+                       weight_op="GDRQ", wbits=wbits, abits=abits)
 
 
 def resnet50(num_classes=1000):

@@ -42,6 +42,12 @@ class WQuantItem(C.Structure):
                 ("k", _i32), ("rs", _i32), ("c_real", _i32), ("c", _i32), ("k_pad", _i32), ("nbits", _i32)]
 
 
+class WGdrqItem(C.Structure):
+    _fields_ = [("master", _P), ("qw", _P), ("unit", _P), ("alpha", _P), ("w_codes", _P), ("w_krsc", _P),
+                ("w_crsk", _P), ("k", _i32), ("rs", _i32), ("c_real", _i32), ("c", _i32), ("k_pad", _i32),
+                ("nbits", _i32), ("fix_alpha", _i32), ("ktimes", _f32)]
+
+
 class PoolDesc(C.Structure):
     _fields_ = [(n, _i32) for n in ("dtype", "n", "h", "w", "c", "r", "s", "stride_h", "stride_w", "pad_h", "pad_w",
                                    "type", "global_pool", "p", "q")]
@@ -134,6 +140,11 @@ SIGNATURES = {
     "rn_pact_fwd": (_i32, [_i32, _i64, _P, _P, _i32, _P, _P, _P, _P]),
     "rn_pact_bwd_ws_bytes": (_i64, [_i64]),
     "rn_pact_bwd": (_i32, [_i32, _i64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rn_gdrq_ws_bytes": (_i64, [_i64]),
+    "rn_gdrq_fwd": (_i32, [_i32, _i64, _i64, _P, _P, _i32, _i32, _f32, _f32, _P, _P, _P, _P, _P]),
+    "rn_gdrq_bwd": (_i32, [_i32, _i64, _P, _P, _P, _P, _P, _P]),
+    "rn_weight_gdrq_ws_bytes": (_i64, [_i32]),
+    "rn_weight_gdrq_pack": (_i32, [_P, _i32, _i32, _P, _P]),
     "rn_set_tuning": (_i32, [_i32, _i32]),
     "rn_last_error": (C.c_char_p, []),
     "rn_version": (_i32, []),
