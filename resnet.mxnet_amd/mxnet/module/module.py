@@ -1,6 +1,6 @@
 """mx.mod.Module on the MI355X runtime (the object core/solver.py:58-82,115-139,170-171 drives).
 
-bind -> rn.executor.Plan + Executor (static plan of librn calls on one GPU)
+bind -> rn.plan.Plan + rn.executor.Executor (static plan of librn calls on one GPU)
 init_params / set_params / get_params -> flat fp32 master buffer (MXNet OIHW layout at the API)
 init_optimizer -> SGD hyper-parameters, rescale_grad = 1/batch (x workers for dist_* stores)
 forward / backward / update -> librn kernels; gradients all-reduced over RCCL in buckets while
@@ -133,7 +133,8 @@ class Module:
             return
         if inputs_need_grad:
             raise MXNetError("inputs_need_grad is not supported")
-        from rn.executor import Plan, Executor
+        from rn.executor import Executor
+        from rn.plan import Plan
         dshapes = [(d.name, tuple(d.shape)) if isinstance(d, DataDesc) else (d[0], tuple(d[1])) for d in data_shapes]
         lshapes = [(d.name, tuple(d.shape)) if isinstance(d, DataDesc) else (d[0], tuple(d[1]))
                    for d in (label_shapes or [])]
@@ -180,7 +181,7 @@ class Module:
         self.binded = True
 
     def _bind_cpu(self, dshapes, lshapes, for_training):
-        from rn.executor import Plan
+        from rn.plan import Plan
         from rn.cpu_executor import CPUExecutor
         self._slice = None
         self._ctx = self._context[0] if self._context else cpu()

@@ -1,706 +1,28 @@
-"""Lower an mx.sym graph onto librn and run training steps on one MI355X.
+"""Bind a lowered mx.sym graph (rn/plan.py) to librn calls and run training steps on one MI355X.
 
 This replaces what MXNet's Module/executor did under core/solver.py (bind :75,
 forward :115, backward :116, update :121): shape inference, buffer allocation, op dispatch,
 gradient fan-in accumulation (req='add') and the optimizer step -- all as a static plan of
 C-ABI calls on one HIP stream.
 
-Planning (`Plan`) is pure Python and runs without a GPU (it is what the CPU tests check).
+Planning (`Plan`, rn/plan.py) is pure Python and runs without a GPU (it is what the CPU tests check).
 `Executor` allocates device memory through PyTorch (plumbing only) and turns the plan into
-lists of bound C calls. Every compute op is a librn kernel; there is no fallback path.
+lists of bound C calls: named pre-passes, then one `_fwd_<kind>` / `_bwd_<kind>` method per op kind, looked up
+by name. Every compute op is a librn kernel; there is no fallback path (a kind without a binder is an error).
 
 Layout: activations NHWC, channel stride padded to a multiple of 8, dtype bf16 (default) or
 fp32 (`dtype='float32'`, exact-fp32 MFMA path used for parity). Parameters live in ONE flat
 fp32 master buffer (conv / FC weights in KRSC), ordered in reverse forward order so that
 gradient buckets complete front-to-back during backward (RCCL bucketing, rn/dist.py).
 """
-import math
 import os
 
 import numpy as np
 
 from . import lib as L
+from .plan import Plan, PlanError, PlanOp, TensorSpec, _pad8  # noqa: F401  (re-exported: tests, tools, the shim)
 
 F32, BF16 = L.RN_F32, L.RN_BF16
-
-
-def _pad8(c):
-    return (c + 7) // 8 * 8
-
-
-def _parse(v, default=None):
-    from mxnet.symbol import _parse as p  # the shim's attr parser
-    return p(v) if v is not None else default
-
-
-def _tup(v, n=2):
-    from mxnet.symbol import _tup as t
-    return t(v, n)
-
-
-class PlanError(RuntimeError):
-    pass
-
-
-# ============================================================================= plan (CPU)
-class TensorSpec:
-    """An activation tensor: logical NCHW (or (N,F)) shape -> NHWC buffer with padded C."""
-
-    def __init__(self, name, shape, dtype, needs_grad=True, kind="act"):
-        self.name = name
-        self.shape = tuple(shape)
-        if len(shape) == 4:
-            self.n, self.c, self.h, self.w = shape
-        elif len(shape) == 2:
-            self.n, self.c = shape
-            self.h = self.w = 1
-        else:
-            raise PlanError("unsupported activation rank for %s: %s" % (name, shape))
-        self.cp = _pad8(self.c)
-        self.dtype = dtype
-        self.needs_grad = needs_grad
-        self.kind = kind  # act | logits | prob | data_nchw | label
-
-    @property
-    def rows(self):
-        return self.n * self.h * self.w
-
-    @property
-    def numel(self):
-        if self.kind in ("data_nchw", "prob", "label"):
-            return int(np.prod(self.shape))
-        return self.rows * self.cp
-
-
-class PlanOp:
-    def __init__(self, kind, name, **kw):
-        self.kind = kind
-        self.name = name
-        self.__dict__.update(kw)
-
-    def __repr__(self):
-        return "<%s %s>" % (self.kind, self.name)
-
-
-class Plan:
-    """Fused op list for a symbol at fixed input shapes."""
-
-    def __init__(self, symbol, data_shapes, label_shapes=(), dtype="bfloat16", for_training=True):
-        self.symbol = symbol
-        self.dtype = BF16 if dtype in ("bfloat16", "bf16", BF16) else F32
-        self.for_training = for_training
-        self.data_names = [n for n, _ in data_shapes]
-        self.label_names = [n for n, _ in label_shapes]
-        known = dict(list(data_shapes) + list(label_shapes))
-        self.input_shapes = known
-        self.topo = symbol._topo()
-        self._infer(known)
-        self.arg_names = symbol.list_arguments()
-        self.aux_names = symbol.list_auxiliary_states()
-        self.param_names = [n for n in self.arg_names if n not in known]
-        self.tensors = {}
-        self.alias = {}
-        self.ops = []
-        self.qweight = {}  # id(weight Quantization_int8 node) -> quant info
-        self.qweight_gdrq = {}  # id(weight GDRQ node) -> quant info (family "gdrq")
-        self._gdrq_alphas = {}  # alpha variable -> the GDRQ node that owns it
-        self._lower()
-
-    # --- shapes of every node output
-    def _infer(self, known):
-        from mxnet.symbol import _infer_node, _parse as parse
-        shapes = {}
-        for n in self.topo:
-            if n.op == "null":
-                if n.name in known:
-                    shapes[(id(n), 0)] = tuple(known[n.name])
-                elif "__shape__" in n.attrs:
-                    shapes[(id(n), 0)] = tuple(parse(n.attrs["__shape__"]))
-        for n in self.topo:
-            if n.op != "null":
-                _infer_node(n, shapes, False)
-        self.shapes = shapes
-
-    def shape_of(self, node, idx=0):
-        return self.shapes[(id(node), idx)]
-
-    def param_shape(self, name):
-        for n in self.topo:
-            if n.op == "null" and n.name == name:
-                return self.shapes[(id(n), 0)]
-        raise KeyError(name)
-
-    # --- helpers
-    def _consumers(self):
-        cons = {}
-        for n in self.topo:
-            for (i, _) in n.inputs:
-                cons.setdefault(id(i), []).append(n)
-        for n, _ in self.symbol._outputs:
-            cons.setdefault(id(n), []).append(None)  # graph output
-        return cons
-
-    def tensor(self, node):
-        key = id(node)
-        while key in self.alias:
-            key = self.alias[key]
-        return self.tensors[key]
-
-    def _new_tensor(self, node, shape, dtype=None, kind="act", needs_grad=True):
-        t = TensorSpec(node.name, shape, self.dtype if dtype is None else dtype, needs_grad, kind)
-        self.tensors[id(node)] = t
-        return t
-
-    def _var_input(self, node):
-        """Follow identity/Cast/Flatten aliases back; return (node, is_variable)."""
-        while node.op in ("identity", "Cast", "Flatten"):
-            node = node.inputs[0][0]
-        return node
-
-    @staticmethod
-    def _is_quant(node):
-        return node is not None and node.op == "_contrib_Quantization_int8"
-
-    def _quant_info(self, n):
-        """Quantization_int8 attrs (int8_api.py:133-136; semantics clip_grad_quantization_int8.py)."""
-        if _parse(n.attrs.get("quant_mode", "minmax")) != "minmax":
-            raise PlanError("%s: quant_mode other than 'minmax' not supported" % n.name)
-        if int(_parse(n.attrs.get("delay_quant", 0))):
-            raise PlanError("%s: delay_quant > 0 not supported" % n.name)
-        if _parse(n.attrs.get("is_weight_perchannel", False)):
-            raise PlanError("%s: per-channel weight quantization not supported" % n.name)
-        return dict(name=n.name, minmax=n.inputs[1][0].name, ema=float(_parse(n.attrs.get("ema_decay", 0.99))),
-                    nbits=int(_parse(n.attrs.get("nbits", 8))),
-                    is_weight=bool(_parse(n.attrs.get("is_weight", False))))
-
-    def _stem_quant(self, node, cons):
-        """A data Quantization_int8 whose only consumer is the stem conv (folded into its im2col)."""
-        cl = cons.get(id(node), [])
-        return self._is_quant(node) and len(cl) == 1 and cl[0] is not None and cl[0].op == "Convolution" and \
-            self._is_stem(cl[0])
-
-    # --- lowering
-    def _lower(self):
-        cons = self._consumers()
-        topo = self.topo
-        done = set()
-        order = {id(n): i for i, n in enumerate(topo)}
-        data_vars = set(self.data_names)
-        # data / label inputs
-        for n in topo:
-            if n.op == "null" and n.name in data_vars:
-                shp = self.shape_of(n)
-                t = TensorSpec(n.name, shp, F32, needs_grad=False, kind="data_nchw")
-                self.tensors[id(n)] = t
-                self.data_tensor = t
-            elif n.op == "null" and n.name in self.label_names:
-                self.tensors[id(n)] = TensorSpec(n.name, (self.shape_of(n)[0], 1), F32, False, "label")
-        # pre-pass: fused residual adds (conv output consumed only by an add)
-        fused_add_into = {}  # id(conv node) -> (add node, other input node)
-        fused_add_relu = {}  # id(add node) -> relu node
-        for n in topo:
-            if n.op in ("_Plus", "elemwise_add", "ElementWiseSum") and len(n.inputs) == 2:
-                a, b = n.inputs[0][0], n.inputs[1][0]
-                cands = [x for x in (a, b) if x.op == "Convolution" and len(cons.get(id(x), [])) == 1
-                         and id(x) not in fused_add_into and not self._is_stem(x)]
-                if cands:
-                    conv = max(cands, key=lambda x: order[id(x)])
-                    other = b if conv is a else a
-                    if order[id(other)] < order[id(conv)] or other.op == "null":
-                        fused_add_into[id(conv)] = (n, other)
-                        continue
-                cl = cons.get(id(n), [])
-                if len(cl) == 1 and cl[0] is not None and cl[0].op == "Activation" and \
-                        _parse(cl[0].attrs.get("act_type")) == "relu":
-                    fused_add_relu[id(n)] = cl[0]
-        for n in topo:
-            if n.op == "null" or id(n) in done:
-                continue
-            op = n.op
-            if op in ("identity", "Flatten", "Cast"):
-                # Cast is a no-op under the runtime precision policy (bf16 / fp32 compute)
-                src = n.inputs[0][0]
-                if op == "Flatten":
-                    st = self.tensor(src)
-                    if st.kind == "act" and (st.h != 1 or st.w != 1):
-                        raise PlanError("Flatten of a spatial map (%s) is not supported" % n.name)
-                self.alias[id(n)] = id(src) if id(src) not in self.alias else self.alias[id(src)]
-                done.add(id(n))
-            elif op == "Convolution":
-                self._lower_conv(n, cons, fused_add_into.get(id(n)))
-                done.add(id(n))
-                if id(n) in fused_add_into:
-                    addn = fused_add_into[id(n)][0]
-                    self.alias[id(addn)] = id(n)
-                    done.add(id(addn))
-            elif op == "BatchNorm":
-                cl = cons.get(id(n), [])
-                relu_node = None
-                if len(cl) == 1 and cl[0] is not None and cl[0].op == "Activation" and \
-                        _parse(cl[0].attrs.get("act_type")) == "relu":
-                    relu_node = cl[0]
-                src = self._var_input(n.inputs[0][0])
-                stem_consumers = [c for c in cl if c is not None and
-                                  ((c.op == "Convolution" and self._is_stem(c)) or self._stem_quant(c, cons))]
-                if src.op == "null" and src.name in data_vars and stem_consumers and len(cl) == 1:
-                    done.add(id(n))  # folded into the stem conv (bn_data)
-                    continue
-                self._lower_bn(n, relu_node)
-                self.ops[-1].relu_name = relu_node.name if relu_node is not None else None
-                done.add(id(n))
-                if relu_node is not None:
-                    self.alias[id(relu_node)] = id(n)
-                    done.add(id(relu_node))
-            elif op == "_contrib_Quantization_int8":
-                q = self._quant_info(n)
-                src = n.inputs[0][0]
-                if q["is_weight"]:
-                    if src.op != "null":
-                        raise PlanError("%s: weight quantization of a computed tensor" % n.name)
-                    q["param"] = src.name
-                    self.qweight[id(n)] = q
-                elif not self._stem_quant(n, cons):  # (the stem's is folded into its im2col)
-                    x = self.tensor(src)
-                    if x.kind != "act":
-                        raise PlanError("%s: data quantization of a non-activation tensor" % n.name)
-                    y = self._new_tensor(n, x.shape)
-                    self.ops.append(PlanOp("quant", n.name, x=x, y=y, q=q))
-                done.add(id(n))
-            elif self._is_gdrq(n):
-                self._lower_gdrq(n)
-                done.add(id(n))
-            elif op == "_contrib_PACT" or op == "Custom":
-                self._lower_pact(n)
-                done.add(id(n))
-            elif op == "Activation":
-                act = _parse(n.attrs.get("act_type"))
-                if act != "relu":
-                    raise PlanError("Activation %s is not supported" % act)
-                x = self.tensor(n.inputs[0][0])
-                y = self._new_tensor(n, self.shape_of(n))
-                self.ops.append(PlanOp("relu", n.name, x=x, y=y, relu_name=n.name))
-                done.add(id(n))
-            elif op in ("_Plus", "elemwise_add", "ElementWiseSum"):
-                if len(n.inputs) != 2:
-                    raise PlanError("ElementWiseSum with %d inputs not supported" % len(n.inputs))
-                a = self.tensor(n.inputs[0][0])
-                b = self.tensor(n.inputs[1][0])
-                relu_node = fused_add_relu.get(id(n))
-                y = self._new_tensor(n, self.shape_of(n))
-                self.ops.append(PlanOp("add", n.name, a=a, b=b, y=y, relu=relu_node is not None,
-                                       relu_name=relu_node.name if relu_node is not None else None))
-                done.add(id(n))
-                if relu_node is not None:
-                    self.alias[id(relu_node)] = id(n)
-                    done.add(id(relu_node))
-            elif op in ("_contrib_BroadcastScale", "broadcast_add"):
-                self._lower_affine(n, cons, done)
-            elif op == "Pooling":
-                self._lower_pool(n)
-                done.add(id(n))
-            elif op == "FullyConnected":
-                self._lower_fc(n)
-                done.add(id(n))
-            elif op == "SoftmaxOutput":
-                x = self.tensor(n.inputs[0][0])
-                if x.kind != "logits":
-                    raise PlanError("SoftmaxOutput must follow FullyConnected")
-                lab = self.tensors[id(n.inputs[1][0])]
-                y = self._new_tensor(n, (x.n, x.c), F32, kind="prob", needs_grad=False)
-                self.ops.append(PlanOp("softmax", n.name, x=x, label=lab, y=y,
-                                       grad_scale=float(_parse(n.attrs.get("grad_scale", 1.0)))))
-                done.add(id(n))
-            else:
-                raise PlanError("operator %s (%s) is not supported by the MI355X runtime" % (op, n.name))
-        self.outputs = [self.tensor(n) for n, _ in self.symbol._outputs]
-        self._fuse_bn_apply()
-        self._mark_int8()
-
-    def _lower_pact(self, n):
-        """PACT (core/graph_optimize.py:180-187): mx.sym.contrib.PACT or mx.sym.Custom(op_type="PACT_PY"), the
-        activation quantizer with a learned clipping threshold -- out = round(min(x, gamma) / unit) * unit,
-        unit = gamma / (2^nbits - 1) (core/operator/PACT.py:102-144). gamma is an ordinary trainable parameter of
-        shape (1,): it joins the flat parameter / gradient / momentum buffers like a BatchNorm's. The Python
-        forward / backward of the CustomOp are never run; any other Custom op_type has no kernel here."""
-        if n.op == "Custom" and _parse(n.attrs.get("op_type")) != "PACT_PY":
-            raise PlanError("operator Custom (%s, op_type=%s) is not supported by the MI355X runtime"
-                            % (n.name, n.attrs.get("op_type")))
-        if len(n.inputs) != 2:
-            raise PlanError("%s: PACT takes data and gamma" % n.name)
-        g = n.inputs[1][0]
-        if g.op != "null" or g.name in self.input_shapes:
-            raise PlanError("%s: PACT's gamma must be a parameter Variable" % n.name)
-        if any(o.kind == "pact" and o.gamma == g.name for o in self.ops):
-            raise PlanError("%s: gamma %s is shared with another PACT node (not supported)" % (n.name, g.name))
-        nbits = int(_parse(n.attrs.get("nbits", 8)))
-        if not 1 <= nbits <= 16:
-            raise PlanError("%s: PACT nbits %d not supported" % (n.name, nbits))
-        x = self.tensor(n.inputs[0][0])
-        if x.kind != "act":
-            raise PlanError("%s: PACT of a non-activation tensor" % n.name)
-        y = self._new_tensor(n, x.shape)
-        self.ops.append(PlanOp("pact", n.name, x=x, y=y, gamma=g.name, nbits=nbits))
-
-    @staticmethod
-    def _is_gdrq(node):
-        return node is not None and (node.op == "_contrib_GDRQ" or
-                                     (node.op == "Custom" and _parse(node.attrs.get("op_type")) == "GDRQ_PY"))
-
-    def _lower_gdrq(self, n):
-        """GDRQ (core/graph_optimize.py:188-195): mx.sym.contrib.GDRQ or mx.sym.Custom(op_type="GDRQ_PY"), per-tensor
-        form -- out = round(clip(x, -alpha, alpha) / unit) * unit, unit = alpha / (2^nbits - 1), a symmetric signed
-        code for weights and activations alike (core/operator/GDRQ.py:50-190; attribute defaults as GDRQ_PYProp).
-        alpha is an auxiliary state of shape (1,), no parameter: with fix_alpha it keeps the value it was
-        initialised or loaded with; otherwise thr = ktimes * mean|x| moves it before the clip -- a weight's alpha is
-        set to thr, an activation's becomes alpha + lamda * (alpha - thr) in training forwards (the reference's sign).
-        A weight quantizer becomes a record on its convolution (self.qweight_gdrq, straight-through backward); an
-        activation quantizer a "gdrq" op. The Python forward / backward of the CustomOp are never run."""
-        a = n.attrs
-        if int(_parse(a.get("group_size", -1))) != -1:
-            raise PlanError("%s: GDRQ group_size %s not supported (per-tensor thresholds only, group_size=-1)"
-                            % (n.name, a.get("group_size")))
-        if int(_parse(a.get("delay_quant", 0))):
-            raise PlanError("%s: GDRQ delay_quant > 0 not supported" % n.name)
-        if len(n.inputs) != 2:
-            raise PlanError("%s: GDRQ takes data and the auxiliary state alpha" % n.name)
-        av = n.inputs[1][0]
-        if av.op != "null" or av.name in self.input_shapes:
-            raise PlanError("%s: GDRQ's alpha must be an auxiliary state Variable" % n.name)
-        if av.name in self._gdrq_alphas:
-            raise PlanError("%s: alpha %s is shared with GDRQ node %s (not supported)"
-                            % (n.name, av.name, self._gdrq_alphas[av.name]))
-        self._gdrq_alphas[av.name] = n.name
-        nbits = int(_parse(a.get("nbits", 4)))
-        if not 1 <= nbits <= 16:
-            raise PlanError("%s: GDRQ nbits %d not supported" % (n.name, nbits))
-        q = dict(family="gdrq", name=n.name, alpha=av.name, nbits=nbits,
-                 fix_alpha=bool(_parse(a.get("fix_alpha", False))), ktimes=float(_parse(a.get("ktimes", 3))),
-                 lamda=float(_parse(a.get("lamda", 0.001))), is_weight=bool(_parse(a.get("is_weight", False))))
-        src = n.inputs[0][0]
-        if q["is_weight"]:
-            if src.op != "null":
-                raise PlanError("%s: weight quantization of a computed tensor" % n.name)
-            q["param"] = src.name
-            self.qweight_gdrq[id(n)] = q
-            return
-        x = self.tensor(src)
-        if x.kind != "act":
-            raise PlanError("%s: GDRQ of a non-activation tensor" % n.name)
-        y = self._new_tensor(n, x.shape)
-        self.ops.append(PlanOp("gdrq", n.name, x=x, y=y, alpha=av.name, nbits=nbits, fix_alpha=q["fix_alpha"],
-                               ktimes=q["ktimes"], lamda=q["lamda"]))
-
-    def _nonneg(self, t):
-        """Is activation tensor `t` known to be >= 0: written by a BatchNorm with fused ReLU, a relu op, an add
-        with ReLU, or a pooling of one of those (PACT has no lower clip: only then are its codes 0 .. 2^nbits - 1)?"""
-        for op in self.ops:
-            if op.y is t:
-                if op.kind in ("bn", "add"):
-                    return bool(op.relu)
-                return op.kind == "relu" or (op.kind == "pool" and self._nonneg(op.x))
-        return False
-
-    def _mark_int8(self):
-        """Quantized convolutions (a Quantization_int8 on both the data and the weight: resnet_int8,
-        attach_quantize_node) whose input quantizer can also emit int8 codes run their forward on the
-        int8 MFMAs (rn_conv_fwd_i8): exact integer sums of the codes, scaled by the two units, instead
-        of bf16 / fp32 products of the fake-quantized values. RN_INT8_MFMA=0: the fake-quant path.
-        A PACT input quantizer qualifies with nbits <= 7 (its codes reach 2^nbits - 1) over a tensor known to be
-        non-negative (_nonneg); otherwise its convolution multiplies the fake-quantized values. A GDRQ quantizer's
-        codes are signed, -L .. L with L = 2^nbits - 1: it qualifies with nbits <= 7 on the data side whatever its
-        input's sign, and on the weight side (Quantization_int8 weights: nbits <= 8); mixed pairs qualify side by
-        side."""
-        producer = {id(op.y): op for op in self.ops if op.kind in ("quant", "pact", "gdrq")}
-        on = os.environ.get("RN_INT8_MFMA", "1") != "0"
-        for op in self.ops:
-            if op.kind in ("quant", "pact", "gdrq"):
-                op.emit_codes = False
-            if op.kind in ("pact", "gdrq"):
-                op.codes_wgrad = False  # (never for PACT / GDRQ: the values are always written)
-        for op in self.ops:
-            if op.kind != "conv":
-                continue
-            q = producer.get(id(op.x))
-            if q is not None and q.kind == "pact":
-                q_ok = q.nbits <= 7 and self._nonneg(q.x)
-            elif q is not None and q.kind == "gdrq":
-                q_ok = q.nbits <= 7  # (signed codes -L .. L, L = 2^nbits - 1 <= 127; the input's sign is free)
-            else:
-                q_ok = q is not None and q.q["nbits"] <= 8
-            # (a GDRQ weight's codes reach 2^nbits - 1, a Quantization_int8 weight's 2^(nbits - 1) - 1)
-            w_ok = op.qweight is not None and \
-                op.qweight["nbits"] <= (7 if op.qweight.get("family") == "gdrq" else 8)
-            op.int8 = bool(on and w_ok and q_ok and op.groups == 1 and op.x.cp % 16 == 0 and
-                           getattr(op, "xf", None) is None)
-            op.qsrc = q if op.int8 else None
-            if op.int8:
-                q.emit_codes = True
-        # (round 4's opt-in RN_QUANT_DEFER -- the values expanded from the codes on the weight-gradient stream
-        # by rn_quant_int8_expand -- measured 4 % slower on C5 and was removed in round 5; the weight gradients
-        # multiply the codes instead, codes_wgrad)
-        users = {}
-        for op in self.ops:
-            for k in ("x", "a", "b", "res", "label"):
-                t = getattr(op, k, None)
-                if t is not None and hasattr(t, "numel"):
-                    users.setdefault(id(t), []).append(op)
-        for op in self.ops:
-            if op.kind == "quant":
-                op.value_users = users.get(id(op.y), [])
-                op.codes_wgrad = False  # (the executor decides: _codes_wgrad)
-
-    def _fuse_bn_apply(self):
-        """BatchNorm+ReLU whose output feeds ONLY 1x1 convolutions (act1 -> conv1 / sc, act3 -> conv3
-        of the pre-activation units, symbol/resnet.py:17-31) or poolings (relu0 -> pool0 of the stem and
-        relu1 -> the global pool, symbol/resnet.py:94-97,111-113): the consumers stage max(x*sc+sh, 0)
-        from the BN input while loading (rn_conv_fwd_x / rn_conv_bwd_filter_x / rn_pool_fwd_x) and the
-        BN+ReLU output is never written or read back."""
-        for op in self.ops:
-            op.xf = None
-            if op.kind == "bn":
-                op.apply_fused = False
-            if op.kind == "add":
-                op.bn_a = op.bn_b = op.bn_a_key = None
-        refs = {}
-        for op in self.ops:
-            for key in ("x", "res", "a", "b"):
-                t = getattr(op, key, None)
-                if isinstance(t, TensorSpec):
-                    refs.setdefault(id(t), []).append((op, key))
-        out_ids = {id(t) for t in self.outputs}
-        self._fuse_bn_add(refs, out_ids)
-        # default on since the LDS-DMA tiles apply it (igemm_big_kernel / wgrad_big_kernel XF): 22.82 ->
-        # 22.17 ms per step on one box; RN_BN_APPLY_FUSION=0 writes act1 / act3
-        if os.environ.get("RN_BN_APPLY_FUSION", "1") != "1":
-            return
-        # (the 3x3 stride-1 consumers too -- act2 -> conv2 of stage 1, RN_BN_APPLY_FUSION_3X3, rounds 4-5 -- measured
-        # 0.6 % slower, then equal with the image-band forward: removed in round 6; the band kernels keep their
-        # BN+ReLU-on-load forms, kernel-tested)
-        def xf_ok(u):
-            return u.groups == 1 and not getattr(u, "qweight", None) and tuple(u.kernel) == (1, 1)
-        # (the poolings: rn_pool_fwd_x; round 6, RN_POOL_XF=0 for the A/B)
-        pool_ok = os.environ.get("RN_POOL_XF", "1") == "1"
-        for bn in self.ops:
-            if bn.kind != "bn" or not bn.relu or id(bn.y) in out_ids:
-                continue
-            users = refs.get(id(bn.y), [])
-            ok = users and all(key == "x" and ((u.kind == "conv" and xf_ok(u)) or (u.kind == "pool" and pool_ok))
-                               for u, key in users)
-            if not ok:
-                continue
-            bn.apply_fused = True
-            bn.y.virtual = True
-            for u, _ in users:
-                u.xf = bn
-
-    def _fuse_bn_add(self, refs, out_ids):
-        """The post-activation unit tail (symbol/resnext.py:40-47, symbol/resnet.py:63-74: bn3 (+ the
-        shortcut's BN) -> add -> relu): a BatchNorm without ReLU whose output only this add reads is
-        applied inside the add (rn_bn_apply_add); its output is never written. RN_BN_ADD_FUSION=0 off."""
-        if os.environ.get("RN_BN_ADD_FUSION", "1") != "1":
-            return
-        producer = {id(op.y): op for op in self.ops if op.kind == "bn"}
-        for op in self.ops:
-            if op.kind != "add" or op.a is op.b:
-                continue
-            fused = []
-            for key in ("a", "b"):
-                t = getattr(op, key)
-                bn = producer.get(id(t))
-                if bn is not None and not bn.relu and id(t) not in out_ids and len(refs.get(id(t), [])) == 1:
-                    fused.append((key, bn))
-            if not fused:
-                continue
-            op.bn_a_key, op.bn_a = fused[0]
-            op.bn_b = fused[1][1] if len(fused) == 2 else None
-            for _, bn in fused:
-                bn.apply_fused = True
-                bn.y.virtual = True
-
-    def _is_stem(self, conv_node):
-        src = conv_node.inputs[0][0]
-        shp = self.shape_of(src)
-        return len(shp) == 4 and shp[1] % 8 != 0
-
-    def _param_node(self, node, idx):
-        p = node.inputs[idx][0]
-        if self._is_quant(p) and id(p) in self.qweight:
-            return self.qweight[id(p)]["param"]
-        if id(p) in self.qweight_gdrq:
-            return self.qweight_gdrq[id(p)]["param"]
-        if p.op != "null":
-            raise PlanError("%s: computed weights are not supported" % node.name)
-        return p.name
-
-    def _weight_quant(self, node, idx=1):
-        p = node.inputs[idx][0]
-        return self.qweight.get(id(p)) if self._is_quant(p) else self.qweight_gdrq.get(id(p))
-
-    def _conv_attrs(self, n):
-        k = _tup(n.attrs["kernel"])
-        st = _tup(n.attrs.get("stride", (1, 1))) or (1, 1)
-        pd = _tup(n.attrs.get("pad", (0, 0))) or (0, 0)
-        dl = _tup(n.attrs.get("dilate", (1, 1))) or (1, 1)
-        g = int(_parse(n.attrs.get("num_group", 1)))
-        if dl != (1, 1):
-            raise PlanError("%s: dilation not supported" % n.name)
-        return k, st, pd, g
-
-    def _lower_conv(self, n, cons, fused):
-        k, st, pd, g = self._conv_attrs(n)
-        xshape = self.shape_of(n.inputs[0][0])
-        yshape = self.shape_of(n)
-        wname = self._param_node(n, 1)
-        if not _parse(n.attrs.get("no_bias", False)):
-            raise PlanError("%s: convolution bias not supported" % n.name)
-        y = self._new_tensor(n, yshape)
-        if self._is_stem(n):
-            if g != 1:
-                raise PlanError("%s: grouped stem convolution not supported" % n.name)
-            src = self._var_input(n.inputs[0][0])
-            squant = None
-            if self._is_quant(src):
-                squant = self._quant_info(src)
-                src = self._var_input(src.inputs[0][0])
-            bn = None
-            if src.op == "BatchNorm":
-                bn = src
-                src = self._var_input(bn.inputs[0][0])
-                if not _parse(bn.attrs.get("fix_gamma", True)):
-                    raise PlanError("stem BatchNorm must have fix_gamma=True")
-            if not (src.op == "null" and src.name in self.data_names):
-                raise PlanError("%s: a conv over %d channels must read the data input" % (n.name, xshape[1]))
-            kc = _pad8(k[0] * k[1] * xshape[1])
-            kc = (kc + 31) // 32 * 32
-            op = PlanOp("stem", n.name, x=self.tensors[id(src)], y=y, weight=wname, kernel=k, stride=st, pad=pd,
-                        kc=kc, bn=None, quant=squant, qweight=self._weight_quant(n))
-            if bn is not None:
-                op.bn = dict(name=bn.name, gamma=self._param_node(bn, 1), beta=self._param_node(bn, 2),
-                             mean=bn.inputs[3][0].name, var=bn.inputs[4][0].name,
-                             eps=float(_parse(bn.attrs.get("eps", 1e-3))),
-                             momentum=float(_parse(bn.attrs.get("momentum", 0.9))),
-                             use_global_stats=bool(_parse(bn.attrs.get("use_global_stats", False))))
-            self.ops.append(op)
-            return
-        x = self.tensor(n.inputs[0][0])
-        if x.kind != "act":
-            raise PlanError("%s: convolution over the raw data input needs C %% 8 != 0 (stem) here" % n.name)
-        res = None
-        if fused is not None:
-            res = self.tensor(fused[1])
-        if g != 1 and (xshape[1] % 8 or yshape[1] % 8):
-            raise PlanError("%s: grouped convolution needs channel counts that are multiples of 8" % n.name)
-        self.ops.append(PlanOp("conv", n.name, x=x, y=y, weight=wname, kernel=k, stride=st, pad=pd, res=res,
-                               groups=g, qweight=self._weight_quant(n)))
-
-    def _lower_bn(self, n, relu_node):
-        x = self.tensor(n.inputs[0][0])
-        shape = self.shape_of(n)
-        y = self._new_tensor(n, shape)
-        self.ops.append(PlanOp("bn", n.name, x=x, y=y, relu=relu_node is not None,
-                               gamma=self._param_node(n, 1), beta=self._param_node(n, 2),
-                               mean=n.inputs[3][0].name, var=n.inputs[4][0].name,
-                               eps=float(_parse(n.attrs.get("eps", 1e-3))),
-                               momentum=float(_parse(n.attrs.get("momentum", 0.9))),
-                               fix_gamma=bool(_parse(n.attrs.get("fix_gamma", True))),
-                               use_global_stats=bool(_parse(n.attrs.get("use_global_stats", False)))))
-
-    def _chan_param(self, node_idx, c):
-        """Name of a per-channel parameter Variable ((C,) or (1,C,1,1)), else None."""
-        v = node_idx[0]
-        shp = self.shapes.get((id(v), node_idx[1]))
-        if v.op != "null" or v.name in self.data_names or shp is None:
-            return None
-        if int(np.prod(shp)) != c or (len(shp) == 4 and shp[1] != c):
-            return None
-        return v.name
-
-    def _lower_affine(self, n, cons, done):
-        """Per-channel affine y = [relu](x * scale + bias): the BroadcastScale -> broadcast_add pair that
-        merge_bn folds an inference BatchNorm into (core/graph_optimize.py:90-93), a standalone
-        broadcast_add of a per-channel parameter, or (two same-shape tensors) a plain add."""
-        x = self.tensor(n.inputs[0][0])
-        c = x.c
-        scale = bias = None
-        last = n
-        if n.op == "_contrib_BroadcastScale":
-            scale = self._chan_param(n.inputs[1], c)
-            if scale is None:
-                raise PlanError("%s: BroadcastScale needs a per-channel (1,C,1,1) scaler Variable" % n.name)
-            cl = cons.get(id(n), [])
-            if len(cl) == 1 and cl[0] is not None and cl[0].op == "broadcast_add" and cl[0].inputs[0][0] is n:
-                bias = self._chan_param(cl[0].inputs[1], c)
-                if bias is not None:
-                    last = cl[0]
-        else:
-            bias = self._chan_param(n.inputs[1], c)
-            if bias is None:
-                other = self.tensor(n.inputs[1][0])
-                if other.shape != x.shape:
-                    raise PlanError("%s: broadcast_add of %s and %s not supported" % (n.name, x.shape, other.shape))
-                y = self._new_tensor(n, self.shape_of(n))
-                self.ops.append(PlanOp("add", n.name, a=x, b=other, y=y, relu=False, relu_name=None))
-                done.add(id(n))
-                return
-        if x.kind != "act":
-            raise PlanError("%s: per-channel affine over a non-activation tensor" % n.name)
-        cl = cons.get(id(last), [])
-        relu_node = None
-        if len(cl) == 1 and cl[0] is not None and cl[0].op == "Activation" and \
-                _parse(cl[0].attrs.get("act_type")) == "relu":
-            relu_node = cl[0]
-        y = self._new_tensor(n, self.shape_of(n))
-        self.ops.append(PlanOp("affine", n.name, x=x, y=y, gamma=scale, beta=bias, relu=relu_node is not None,
-                               relu_name=relu_node.name if relu_node is not None else None))
-        done.add(id(n))
-        for extra in (last, relu_node):
-            if extra is not None and extra is not n:
-                self.alias[id(extra)] = id(n)
-                done.add(id(extra))
-
-    def _lower_pool(self, n):
-        x = self.tensor(n.inputs[0][0])
-        y = self._new_tensor(n, self.shape_of(n))
-        ptype = _parse(n.attrs.get("pool_type", "max"))
-        if ptype not in ("max", "avg"):
-            raise PlanError("pool_type %s not supported" % ptype)
-        glob = bool(_parse(n.attrs.get("global_pool", False)))
-        if _parse(n.attrs.get("pooling_convention", "valid")) != "valid" and not glob:
-            raise PlanError("pooling_convention other than 'valid' not supported")
-        k = _tup(n.attrs.get("kernel", (1, 1))) or (1, 1)
-        st = _tup(n.attrs.get("stride", (1, 1))) or (1, 1)
-        pd = _tup(n.attrs.get("pad", (0, 0))) or (0, 0)
-        self.ops.append(PlanOp("pool", n.name, x=x, y=y, type=ptype, global_pool=glob, kernel=k, stride=st, pad=pd))
-
-    def _lower_fc(self, n):
-        x = self.tensor(n.inputs[0][0])
-        if x.h != 1 or x.w != 1:
-            raise PlanError("%s: FullyConnected over a spatial map is not supported" % n.name)
-        nh = int(_parse(n.attrs["num_hidden"]))
-        no_bias = bool(_parse(n.attrs.get("no_bias", False)))
-        y = self._new_tensor(n, (x.n, nh), F32, kind="logits")
-        self.ops.append(PlanOp("fc", n.name, x=x, y=y, weight=self._param_node(n, 1),
-                               bias=None if no_bias else self._param_node(n, 2), nh=nh,
-                               qweight=self._weight_quant(n)))
-
-    def summary(self):
-        kinds = {}
-        for op in self.ops:
-            kinds[op.kind] = kinds.get(op.kind, 0) + 1
-        return kinds
-
-    def train_flops(self):
-        """Algorithmic FLOP per step (2 FLOP/MAC): fwd + dgrad (except the stem) + wgrad."""
-        total = 0
-        for op in self.ops:
-            if op.kind in ("conv", "stem"):
-                y = op.y
-                cin = op.x.shape[1] // getattr(op, "groups", 1)
-                macs = y.n * y.h * y.w * y.c * cin * op.kernel[0] * op.kernel[1]
-                total += 2 * macs * (2 if op.kind == "stem" else 3)
-            elif op.kind == "fc":
-                total += 2 * op.x.n * op.x.c * op.nh * 3
-        return total
 
 
 # ============================================================================= executor (GPU)
@@ -796,9 +118,6 @@ class Executor:
         self._fwd_train, self._fwd_infer, self._bwd = [], [], []
         # Quantization_int8: activation EMA states initialise from the first training batch
         self._qfirst = L.C.c_int32(1)
-        # SGD writes the dense weights' compute copies itself (rn_sgd_mom_update_pack); 0 = the
-        # separate pack launches after every update
-        self.fuse_packs = os.environ.get("RN_FUSED_PACK", "1") == "1"
         self._build_params()
         self._alloc_acts()
         self._build_forward()
@@ -1041,7 +360,7 @@ class Executor:
         for op in plan.ops:
             if op.kind != "quant":
                 continue
-            us = getattr(op, "value_users", [])
+            us = op.value_users
             ok = on and op.emit_codes and bool(us) and \
                 all(u.kind == "conv" and u.int8 and u.qsrc is op for u in us)
             if ok:
@@ -1053,9 +372,9 @@ class Executor:
 
     # ------------------------------------------------------------------ forward
     def _build_forward(self):
+        """The pre-passes that stamp the ops, then one _fwd_<kind>(op, F, I) per op appending its calls to the
+        train-mode (F) and infer-mode (I) lists, then the batched weight packs."""
         plan = self.plan
-        sp = self._sp()
-        ws_bytes = 64
         self._descs = []  # keep ctypes structs alive
         self._codes_wgrad(plan)
         self.packs = []   # weight pack calls (bind time / set_params)
@@ -1069,11 +388,31 @@ class Executor:
         # the grouped layers' repacks in one rn_conv_weight_pack_multi (RN_GPACK_BATCH=0: one call each)
         self._gpack_batch = os.environ.get("RN_GPACK_BATCH", "1") == "1"
         self._gpacks = []
-        self.bn_state = {}
-        stem_ws = 64
-        # BatchNorm statistics straight from the producing conv's epilogue (no separate stats pass)
-        producer = {}
+        self._stem_ws_numel = 64  # (grown by _fwd_stem)
+        # in this order: _mark_quant_bn reads the part_src that _mark_bn_stats sets; the binders below read the
+        # descriptors, the workspaces and all of these marks
+        self._mark_bn_stats()
+        self._describe_ops()
+        self._mark_quant_bn()
         for op in plan.ops:
+            F, I = [], []
+            # (_weight_source may append the bind-time quantizer calls of the unbatched path to self.packs: before
+            # the op's own pack)
+            op.wsrc = self._weight_source(op) if op.qweight else \
+                (self._pp(op.weight) if getattr(op, "weight", None) else None)
+            getattr(self, "_fwd_" + op.kind)(op, F, I)
+            self._fwd_train.extend(F)
+            self._fwd_infer.extend(I)
+        self.stem_ws = self._zeros(self._stem_ws_numel, self.torch.float32)
+        self._bind_weight_packs()
+
+    def _mark_bn_stats(self):
+        """BatchNorm statistics straight from the producing conv's epilogue (no separate stats pass): sets
+        conv.bnstats and bn.part_src. The stem's is provisional: _fwd_stem, bound before the BatchNorm that reads
+        part_src, clears both where the stem does not run the band kernel with whole bands per workgroup."""
+        plan = self.plan
+        producer = {}
+        for op in plan.ops:  # (a plan bound again starts clean)
             op.bnstats = False
             op.part_src = None
             if op.kind in ("conv", "stem"):
@@ -1082,22 +421,28 @@ class Executor:
         # fused only where the producer runs the 256-row tile: the 128-row kernel's epilogue costs
         # more than the statistics pass it saves (RN_BN_EPILOGUE_STATS=2: every conv producer)
         stats_mode = os.environ.get("RN_BN_EPILOGUE_STATS", "1")
-        if stats_mode in ("1", "2"):
-            for op in plan.ops:
-                if op.kind == "bn" and not op.use_global_stats:
-                    src = producer.get(id(op.x))
-                    if src is not None and src.kind == "conv" and src.y.c % 8 == 0 and src.y.cp == op.x.cp and \
-                            (stats_mode == "2" or self._big_tile(src, 0) or self._grouped_fuse(src, 0)) and \
-                            not self._depthwise(src):
-                        src.bnstats = True
-                        op.part_src = src
-                    elif src is not None and src.kind == "stem" and src.y.cp == op.x.cp and \
-                            os.environ.get("RN_STEM_BN_STATS", "1") == "1":
-                        # (bn0's statistics from the stem band kernel: kept only where the stem runs it with
-                        # whole bands per workgroup, rn_stem_bnstats_blocks; decided when the stem is built)
-                        src.bnstats = True
-                        op.part_src = src
+        if stats_mode not in ("1", "2"):
+            return
         for op in plan.ops:
+            if op.kind == "bn" and not op.use_global_stats:
+                src = producer.get(id(op.x))
+                if src is not None and src.kind == "conv" and src.y.c % 8 == 0 and src.y.cp == op.x.cp and \
+                        (stats_mode == "2" or self._big_tile(src, 0) or self._grouped_fuse(src, 0)) and \
+                        not self._depthwise(src):
+                    src.bnstats = True
+                    op.part_src = src
+                elif src is not None and src.kind == "stem" and src.y.cp == op.x.cp:
+                    # (bn0's statistics from the stem band kernel: kept only where the stem runs it with
+                    # whole bands per workgroup, rn_stem_bnstats_blocks; decided when the stem is built)
+                    src.bnstats = True
+                    op.part_src = src
+
+    def _describe_ops(self):
+        """The BatchNorm descriptors (held by reference by every call bound from here on: the backward writes
+        clip / clip2 / dy2 and _fwd_bn xmm into them afterwards, and the calls see it) and the two workspaces sized
+        over all ops."""
+        ws_bytes = 64
+        for op in self.plan.ops:
             if op.kind == "bn":
                 d = L.BNDesc(dtype=self.dtype, m=op.x.rows, c=op.x.cp, c_real=op.x.c, eps=op.eps,
                              momentum=op.momentum, fix_gamma=int(op.fix_gamma), relu=int(op.relu))
@@ -1114,15 +459,17 @@ class Executor:
                                       momentum=b.get("momentum", 0.9), fix_gamma=1, relu=0)
                 ws_bytes = max(ws_bytes, 2 * 8 * 256 * 4 + 64)
         self.ws = self._zeros(ws_bytes // 4 + 16, self.torch.float32)
-        wsp = self._p(self.ws)
+        self._wsp = self._p(self.ws)
         self.qws = self._zeros(4096, self.torch.float32)
-        qwsp = self._p(self.qws)
-        # activation quantizers whose BatchNorm(+ReLU) input nothing else reads (the int8 graph): the
-        # quantizer applies the BN on load (rn_quant_int8_fwd_codes_bn, bit-identical) and the BN's
-        # output is never written -- with the folded straight-through backward nothing reads it
-        # (RN_QUANT_BN_FUSE=0: rn_bn_apply + rn_quant_int8_fwd_codes)
-        groups = self._quant_groups() if os.environ.get("RN_QUANT_BN_FUSE", "1") == "1" else {}
-        for op in plan.ops:
+        self._qwsp = self._p(self.qws)
+
+    def _mark_quant_bn(self):
+        """Activation quantizers whose BatchNorm(+ReLU) input nothing else reads (the int8 graph): the
+        quantizer applies the BN on load (rn_quant_int8_fwd_codes_bn, bit-identical) and the BN's
+        output is never written -- with the folded straight-through backward nothing reads it. Where
+        cp % 16 != 0 or a quantizer emits no codes: rn_bn_apply + rn_quant_int8_fwd_codes. Reads bn.part_src
+        (_mark_bn_stats) and op.int8."""
+        for op in self.plan.ops:  # (a plan bound again starts clean)
             op.bn_src = None
             op.bn_peer = None  # the second quantizer of the same BN output (written by this op's call)
             op.bn_lead = None  # (the quantizer whose call writes this one)
@@ -1130,321 +477,326 @@ class Executor:
             op.mm_src = None
             if op.kind == "bn":
                 op.apply_in_quant = False
-        for bn, qs in groups.values():
+        for bn, qs in self._quant_groups().values():
             if all(q.emit_codes for q in qs) and bn.x.cp % 16 == 0:
                 bn.apply_in_quant = True
                 qs[0].bn_src = bn
                 if len(qs) == 2:
                     qs[0].bn_peer, qs[1].bn_lead = qs[1], qs[0]
                 # the quantizers' max from the producing int8 conv's per-block extremes of the BN input
-                # (rn_conv_fwd_i8_mm -> rn_bn_desc.xmm) instead of a pass over it (RN_QUANT_BN_MM=0: the pass)
+                # (rn_conv_fwd_i8_mm -> rn_bn_desc.xmm) instead of a pass over it
                 src = bn.part_src
-                if src is not None and getattr(src, "int8", False) and bn.relu and self.dtype == BF16 and \
-                        os.environ.get("RN_QUANT_BN_MM", "1") == "1":
+                if src is not None and src.int8 and bn.relu and self.dtype == BF16:
                     src.want_mm = True
                     src.mm_gamma = None if bn.fix_gamma else bn.gamma  # (its sign is the BN scale's)
                     bn.mm_src = src
-        for op in plan.ops:
-            F, I = [], []  # train-mode, infer-mode call lists
-            op.wsrc = self._weight_source(op, qwsp, sp) if getattr(op, "qweight", None) else \
-                (self._pp(op.weight) if getattr(op, "weight", None) else None)
-            if op.kind == "stem":
-                # conv0 over the 3-channel input: bn_data statistics straight from the NCHW batch, one
-                # pass writing the normalised NHWC-8 copy, then the implicit GEMM in its small-C mode
-                # (k = tap*8 + c flattened; symbol/resnet.py:90-93)
-                x, y = op.x, op.y
-                dfull = self._conv_desc(x.n, x.h, x.w, 8, x.c, y.c, op.kernel, op.stride, op.pad)
-                assert (dfull.p, dfull.q) == (y.h, y.w), (op.name, dfull.p, dfull.q, y.h, y.w)
-                op.dfull = op.desc = dfull
-                # bf16 (not int8-quantized): the zero-bordered NHWC4 image instead of NHWC-8 (the
-                # reduction runs over 8x8 taps x 4 channels = 256 instead of 7x7 x 8 = 392, and no
-                # in-image tests); its border is zeroed here once, the prepare pass writes the inside
-                hp = max(x.h + 2 * op.pad[0], (dfull.p - 1) * op.stride[0] + 8)
-                wp = max(x.w + 2 * op.pad[1], (dfull.q - 1) * op.stride[1] + 8)
-                op.p4 = None
-                # (the NHWC4 stem's weight gradient adds with atomics: not in the deterministic mode)
-                if self.dtype == BF16 and not op.quant and os.environ.get("RN_STEM_P4", "1") == "1" and \
-                        os.environ.get("RN_DETERMINISTIC", "0") != "1" and \
-                        self.lib.rn_stem_p4_supported(L.C.byref(dfull), hp, wp):
-                    op.p4 = (hp, wp)
-                    op.x8 = self._zeros(x.n * hp * wp * 4, self.tdtype)
-                    op.wk = self._zeros(y.c * 256, self.tdtype)
-                    c_ = self._call("rn_stem_weight_pack_p4", L.C.byref(dfull), op.wsrc, self._p(op.wk), sp)
-                    self.packs.append(c_)
-                    self.unfused_packs.append(c_)
-                else:
-                    op.x8 = self._zeros(x.n * x.h * x.w * 8, self.tdtype)
-                    op.wk = self._zeros(y.c * op.kernel[0] * op.kernel[1] * 8, self.tdtype)
-                    self._add_pack(op, dfull, op.wk, None, sp)
-                stem_ws = max(stem_ws, y.h * y.w * y.cp + y.h * op.kernel[1] * y.c + y.c * op.kernel[0] * op.kernel[1] + 64)
-                xnchw = self._in_ptr  # the current input buffer (double-buffered H2D pipeline)
-                op.bnbuf = self._zeros(4 * 8, self.torch.float32)
-                sm, si, sc, sh = [L.C.c_void_p(op.bnbuf.data_ptr() + 32 * i) for i in range(4)]
-                op.bn_ptrs = (sm, si, sc, sh)
-                b = op.bn
-                if b:
-                    bnargs = (self._pp(b["gamma"]), self._pp(b["beta"]), self._ap(b["mean"]), self._ap(b["var"]))
-                    mode_f = 1 if b["use_global_stats"] else 0
-                    mode_i = 1
-                else:
-                    bnargs = (None, None, None, None)
-                    mode_f = mode_i = 2
-                for lst, mode in ((F, mode_f), (I, mode_i)):
-                    if op.p4:
-                        lst.append(self._call("rn_stem_prepare_p4", L.C.byref(op.bn_desc), xnchw, x.n, x.c, x.h, x.w,
-                                              self._p(op.x8), op.p4[0], op.p4[1], op.pad[0], op.pad[1], mode,
-                                              *bnargs, sm, si, sc, sh, wsp, sp))
-                    else:
-                        lst.append(self._call("rn_stem_prepare", L.C.byref(op.bn_desc), xnchw, x.n, x.c, x.h, x.w,
-                                              self._p(op.x8), mode, *bnargs, sm, si, sc, sh, wsp, sp))
-                if op.quant:
-                    q = op.quant
-                    for lst, tr in ((F, 1), (I, 0)):
-                        lst.append(self._call("rn_quant_int8_fwd", self.dtype, x.n * x.h * x.w * 8, self._p(op.x8),
-                                              self._p(op.x8), self._ap(q["minmax"]), 0, tr, q["ema"], self._qfirst,
-                                              q["nbits"], qwsp, sp))
-                nblk = int(self.lib.rn_stem_bnstats_blocks(L.C.byref(dfull), *op.p4)) if (op.p4 and op.bnstats) else 0
-                if op.bnstats and nblk <= 0:  # the BatchNorm runs its own statistics pass
-                    op.bnstats = False
-                    for o in plan.ops:
-                        if getattr(o, "part_src", None) is op:
-                            o.part_src = None
-                if op.p4:
-                    c_ = self._call("rn_stem_conv_fwd_p4", L.C.byref(dfull), self._p(op.x8), self._p(op.wk),
-                                    self._p(self.act(y)), op.p4[0], op.p4[1], sp)
-                    I.append(c_)
-                    if op.bnstats:  # + bn0's statistics of the stored output, one block per band workgroup
-                        op.part_blocks, op.part_rows = nblk, y.rows // nblk
-                        op.part = self._zeros(nblk * 3 * y.cp, self.torch.float32)
-                        F.append(self._call("rn_stem_conv_fwd_p4_bnstats", L.C.byref(dfull), self._p(op.x8),
-                                            self._p(op.wk), self._p(self.act(y)), op.p4[0], op.p4[1],
-                                            self._p(op.part), sp))
-                    else:
-                        F.append(c_)
-                else:
-                    I.append(self._call("rn_conv_fwd", L.C.byref(dfull), self._p(op.x8), self._p(op.wk),
-                                        self._p(self.act(y)), self.dtype, None, None, sp))
-                    F.append(self._conv_fwd_call(op, dfull, self._p(op.x8), None, sp))
-            elif op.kind == "conv":
-                x, y = op.x, op.y
-                d = self._conv_desc(x.n, x.h, x.w, x.cp, x.c, y.c, op.kernel, op.stride, op.pad, op.groups)
-                assert (d.p, d.q) == (y.h, y.w), (op.name, d.p, d.q, y.h, y.w)
-                op.desc = d
-                op.wc = self._zeros(self.lib.rn_conv_pack_numel(L.C.byref(d), 1), self.tdtype)
-                wgdrq = op in self._wg_ops
-                if wgdrq and op.groups == 1 and not getattr(op, "int8", False):
-                    # (both compute copies written by rn_weight_gdrq_pack; their padding stays zero)
-                    op.wk = self._zeros(self.lib.rn_conv_pack_numel(L.C.byref(d), 0), self.tdtype)
-                elif getattr(op, "int8", False):
-                    # forward copy: the int8 codes (KRSC); the data-gradient copy stays the
-                    # fake-quantized values in the compute dtype (STE backward)
-                    op.wk = None
-                    op.wk8 = self.torch.zeros(int(self.lib.rn_conv_pack_numel(L.C.byref(d), 0)),
-                                              dtype=self.torch.int8, device=self.device)
-                    if not self._wq_batch and not wgdrq:  # (batched: written by rn_weight_quant_pack)
-                        self._add_pack(op, d, None, op.wc, sp)
-                        c_ = self._call("rn_conv_weight_pack_i8", L.C.byref(d), self._pp(op.weight),
-                                        self._p(op.wunit), self._p(op.wk8), sp)
-                        self.packs.append(c_)
-                        self.unfused_packs.append(c_)
-                else:
-                    op.wk = self._zeros(self.lib.rn_conv_pack_numel(L.C.byref(d), 0), self.tdtype)
-                    self._add_pack(op, d, op.wk, op.wc, sp)
-                res = self._p(self.act(op.res)) if op.res is not None else None
-                xin = self._p(self.act(op.xf.x)) if op.xf is not None else self._p(self.act(x))
-                I.append(self._conv_fwd_call(op, d, xin, res, sp, stats=False))
-                F.append(self._conv_fwd_call(op, d, xin, res, sp))
-            elif op.kind == "bn":
-                x, y = op.x, op.y
-                c = x.cp
-                op.buf = self._zeros(4 * c, self.torch.float32)
-                op.sm, op.si, op.sc, op.sh = [L.C.c_void_p(op.buf.data_ptr() + 4 * c * i) for i in range(4)]
-                gamma = self._pp(op.gamma)
-                # fused into the 1x1 consumers' loads or the quantizer's: coefficients only
-                yptr = None if op.apply_fused or op.apply_in_quant else self._p(self.act(y))
-                if op.mm_src is not None and getattr(op.mm_src, "part_mm", None) is not None:
-                    op.desc.xmm = op.mm_src.part_mm.data_ptr()
-                    op.desc.xmm_blocks = op.mm_src.part_blocks
-                infer = self._call("rn_bn_fwd_infer", L.C.byref(op.desc), self._p(self.act(x)), yptr,
-                                   gamma, self._pp(op.beta), self._ap(op.mean), self._ap(op.var), op.sc, op.sh, sp)
-                if op.use_global_stats:
-                    F.append(infer)
-                elif op.part_src is not None:
-                    s_ = op.part_src
-                    F.append(self._call("rn_bn_fwd_train_part", L.C.byref(op.desc), self._p(s_.part), s_.part_blocks,
-                                        s_.part_rows, s_.y.cp, self._p(self.act(x)), yptr, gamma,
-                                        self._pp(op.beta), self._ap(op.mean), self._ap(op.var), op.sm, op.si, op.sc,
-                                        op.sh, wsp, sp))
-                else:
-                    F.append(self._call("rn_bn_fwd_train", L.C.byref(op.desc), self._p(self.act(x)),
-                                        yptr, gamma, self._pp(op.beta), self._ap(op.mean),
-                                        self._ap(op.var), op.sm, op.si, op.sc, op.sh, wsp, sp))
-                I.append(infer)
-            elif op.kind == "affine":
-                # y = [relu](x*scale + bias) with per-channel parameters copied into channel-padded
-                # coefficient vectors each forward (set_params / SGD may change them)
-                x, y = op.x, op.y
-                c = x.cp
-                op.buf = self._zeros(4 * c, self.torch.float32)
-                if op.gamma is None:
-                    op.buf[:x.c] = 1.0
-                op.sc, op.sh, op.zero, op.one = [L.C.c_void_p(op.buf.data_ptr() + 4 * c * i) for i in range(4)]
-                op.buf[3 * c:3 * c + x.c] = 1.0
-                op.desc = L.BNDesc(dtype=self.dtype, m=x.rows, c=c, c_real=x.c, eps=0.0, momentum=0.0,
-                                   fix_gamma=int(op.gamma is None), relu=int(op.relu))
-                for nm, dst in ((op.gamma, op.sc), (op.beta, op.sh)):
-                    if nm is not None:
-                        c_ = self._call("rn_cast", x.c, self._pp(nm), F32, dst, F32, sp)
-                        F.append(c_)
-                        I.append(c_)
-                c_ = self._call("rn_bn_apply", L.C.byref(op.desc), self._p(self.act(x)), self._p(self.act(y)),
-                                op.sc, op.sh, sp)
+
+    def _fwd_stem(self, op, F, I):
+        """conv0 over the 3-channel input: bn_data statistics straight from the NCHW batch, one
+        pass writing the normalised NHWC-8 copy, then the implicit GEMM in its small-C mode
+        (k = tap*8 + c flattened; symbol/resnet.py:90-93)."""
+        sp, wsp = self._spv, self._wsp
+        x, y = op.x, op.y
+        dfull = self._conv_desc(x.n, x.h, x.w, 8, x.c, y.c, op.kernel, op.stride, op.pad)
+        assert (dfull.p, dfull.q) == (y.h, y.w), (op.name, dfull.p, dfull.q, y.h, y.w)
+        op.dfull = op.desc = dfull
+        # bf16 (not int8-quantized): the zero-bordered NHWC4 image instead of NHWC-8 (the
+        # reduction runs over 8x8 taps x 4 channels = 256 instead of 7x7 x 8 = 392, and no
+        # in-image tests); its border is zeroed here once, the prepare pass writes the inside
+        hp = max(x.h + 2 * op.pad[0], (dfull.p - 1) * op.stride[0] + 8)
+        wp = max(x.w + 2 * op.pad[1], (dfull.q - 1) * op.stride[1] + 8)
+        op.p4 = None
+        # (the NHWC4 stem's weight gradient adds with atomics: not in the deterministic mode)
+        if self.dtype == BF16 and not op.quant and os.environ.get("RN_DETERMINISTIC", "0") != "1" and \
+                self.lib.rn_stem_p4_supported(L.C.byref(dfull), hp, wp):
+            op.p4 = (hp, wp)
+            op.x8 = self._zeros(x.n * hp * wp * 4, self.tdtype)
+            op.wk = self._zeros(y.c * 256, self.tdtype)
+            c_ = self._call("rn_stem_weight_pack_p4", L.C.byref(dfull), op.wsrc, self._p(op.wk), sp)
+            self.packs.append(c_)
+            self.unfused_packs.append(c_)
+        else:
+            op.x8 = self._zeros(x.n * x.h * x.w * 8, self.tdtype)
+            op.wk = self._zeros(y.c * op.kernel[0] * op.kernel[1] * 8, self.tdtype)
+            self._add_pack(op, dfull, op.wk, None)
+        self._stem_ws_numel = max(self._stem_ws_numel, y.h * y.w * y.cp + y.h * op.kernel[1] * y.c +
+                                  y.c * op.kernel[0] * op.kernel[1] + 64)
+        xnchw = self._in_ptr  # the current input buffer (double-buffered H2D pipeline)
+        op.bnbuf = self._zeros(4 * 8, self.torch.float32)
+        sm, si, sc, sh = [L.C.c_void_p(op.bnbuf.data_ptr() + 32 * i) for i in range(4)]
+        op.bn_ptrs = (sm, si, sc, sh)
+        b = op.bn
+        if b:
+            bnargs = (self._pp(b["gamma"]), self._pp(b["beta"]), self._ap(b["mean"]), self._ap(b["var"]))
+            mode_f = 1 if b["use_global_stats"] else 0
+            mode_i = 1
+        else:
+            bnargs = (None, None, None, None)
+            mode_f = mode_i = 2
+        for lst, mode in ((F, mode_f), (I, mode_i)):
+            if op.p4:
+                lst.append(self._call("rn_stem_prepare_p4", L.C.byref(op.bn_desc), xnchw, x.n, x.c, x.h, x.w,
+                                      self._p(op.x8), op.p4[0], op.p4[1], op.pad[0], op.pad[1], mode,
+                                      *bnargs, sm, si, sc, sh, wsp, sp))
+            else:
+                lst.append(self._call("rn_stem_prepare", L.C.byref(op.bn_desc), xnchw, x.n, x.c, x.h, x.w,
+                                      self._p(op.x8), mode, *bnargs, sm, si, sc, sh, wsp, sp))
+        if op.quant:
+            q = op.quant
+            for lst, tr in ((F, 1), (I, 0)):
+                lst.append(self._call("rn_quant_int8_fwd", self.dtype, x.n * x.h * x.w * 8, self._p(op.x8),
+                                      self._p(op.x8), self._ap(q["minmax"]), 0, tr, q["ema"], self._qfirst,
+                                      q["nbits"], self._qwsp, sp))
+        nblk = int(self.lib.rn_stem_bnstats_blocks(L.C.byref(dfull), *op.p4)) if (op.p4 and op.bnstats) else 0
+        if op.bnstats and nblk <= 0:  # the BatchNorm runs its own statistics pass
+            op.bnstats = False
+            for o in self.plan.ops:  # (bn0 is bound after this op: its binder sees part_src cleared)
+                if o.part_src is op:
+                    o.part_src = None
+        if op.p4:
+            c_ = self._call("rn_stem_conv_fwd_p4", L.C.byref(dfull), self._p(op.x8), self._p(op.wk),
+                            self._p(self.act(y)), op.p4[0], op.p4[1], sp)
+            I.append(c_)
+            if op.bnstats:  # + bn0's statistics of the stored output, one block per band workgroup
+                op.part_blocks, op.part_rows = nblk, y.rows // nblk
+                op.part = self._zeros(nblk * 3 * y.cp, self.torch.float32)
+                F.append(self._call("rn_stem_conv_fwd_p4_bnstats", L.C.byref(dfull), self._p(op.x8), self._p(op.wk),
+                                    self._p(self.act(y)), op.p4[0], op.p4[1], self._p(op.part), sp))
+            else:
                 F.append(c_)
-                I.append(c_)
-            elif op.kind == "relu":
-                c = self._call("rn_eltwise_add", op.x.numel, self.dtype, self._p(self.act(op.x)), None,
-                               self._p(self.act(op.y)), 1, sp)
-                F.append(c)
-                I.append(c)
-            elif op.kind == "quant":
-                q = op.q
-                for o in (op, op.bn_peer):
-                    if o is not None and o.emit_codes and getattr(o, "codes", None) is None:
-                        # + the int8 codes and unit the consumers' int8 forward reads
-                        o.codes = self.torch.zeros(o.x.numel, dtype=self.torch.int8, device=self.device)
-                        o.unit = self._zeros(1, self.torch.float32)
-                # (codes_wgrad: codes only, the weight gradients multiply them)
-                vout = lambda o: None if o.codes_wgrad else self._p(self.act(o.y))
-                for lst, tr in ((F, 1), (I, 0)):
-                    if op.bn_lead is not None:
-                        pass  # written by its peer's call
-                    elif op.bn_peer is not None:
-                        bn, o2 = op.bn_src, op.bn_peer
-                        lst.append(self._call("rn_quant_int8_fwd_codes_bn2", L.C.byref(bn.desc),
-                                              self._p(self.act(bn.x)), bn.sc, bn.sh, vout(op),
-                                              self._p(op.codes), self._p(op.unit), self._ap(q["minmax"]), q["ema"],
-                                              q["nbits"], vout(o2), self._p(o2.codes),
-                                              self._p(o2.unit), self._ap(o2.q["minmax"]), o2.q["ema"],
-                                              o2.q["nbits"], tr, self._qfirst, qwsp, sp))
-                    elif op.bn_src is not None:
-                        bn = op.bn_src
-                        lst.append(self._call("rn_quant_int8_fwd_codes_bn", L.C.byref(bn.desc),
-                                              self._p(self.act(bn.x)), bn.sc, bn.sh, vout(op),
-                                              self._p(op.codes), self._p(op.unit), self._ap(q["minmax"]), tr,
-                                              q["ema"], self._qfirst, q["nbits"], qwsp, sp))
-                    elif op.emit_codes:
-                        lst.append(self._call("rn_quant_int8_fwd_codes", self.dtype, op.x.numel,
-                                              self._p(self.act(op.x)), vout(op), self._p(op.codes),
-                                              self._p(op.unit), self._ap(q["minmax"]), 0, tr, q["ema"],
-                                              self._qfirst, q["nbits"], qwsp, sp))
-                    else:
-                        lst.append(self._call("rn_quant_int8_fwd", self.dtype, op.x.numel, self._p(self.act(op.x)),
-                                              self._p(self.act(op.y)), self._ap(q["minmax"]), 0, tr, q["ema"],
-                                              self._qfirst, q["nbits"], qwsp, sp))
-            elif op.kind == "pact":
-                # the same in training and inference; gamma is read on the device from the flat master buffer, so
-                # every step (and a replayed graph) sees the value the last update left. The values are always
-                # written; with emit_codes also the int8 codes and the unit the consumers' int8 forward reads
-                op.unit = self._zeros(1, self.torch.float32)
-                op.codes = self.torch.zeros(op.x.numel, dtype=self.torch.int8, device=self.device) \
-                    if op.emit_codes else None
-                c = self._call("rn_pact_fwd", self.dtype, op.x.numel, self._p(self.act(op.x)), self._pp(op.gamma),
-                               op.nbits, self._p(self.act(op.y)), self._p(op.codes), self._p(op.unit), sp)
-                F.append(c)
-                I.append(c)
-            elif op.kind == "gdrq":
-                # alpha is read (and, in training without fix_alpha, first updated) on the device in the aux buffer:
-                # no host synchronisation, a replayed graph sees the current value. Inference never writes it. The
-                # values are always written; with emit_codes also the signed int8 codes and the unit
-                x = op.x
-                op.unit = self._zeros(1, self.torch.float32)
-                op.codes = self.torch.zeros(x.numel, dtype=self.torch.int8, device=self.device) \
-                    if op.emit_codes else None
-                if not op.fix_alpha and self._gdrq_ws is None:
-                    nmax = max(o.x.numel for o in plan.ops if o.kind == "gdrq" and not o.fix_alpha)
-                    self._gdrq_ws = self._zeros(int(self.lib.rn_gdrq_ws_bytes(nmax)) // 4, self.torch.float32)
-                for lst, upd in ((F, int(not op.fix_alpha)), (I, 0)):
-                    lst.append(self._call("rn_gdrq_fwd", self.dtype, x.numel, x.rows * x.c, self._p(self.act(x)),
-                                          self._ap(op.alpha), op.nbits, upd, op.ktimes, op.lamda,
-                                          self._p(self.act(op.y)), self._p(op.codes), self._p(op.unit),
-                                          self._p(self._gdrq_ws) if upd else None, sp))
-            elif op.kind == "add" and getattr(op, "bn_a", None) is not None:
-                bna, bnb = op.bn_a, op.bn_b
-                other = op.b if op.bn_a_key == "a" else op.a
-                c = self._call("rn_bn_apply_add", L.C.byref(bna.desc), self._p(self.act(bna.x)), bna.sc, bna.sh,
-                               self._p(self.act(bnb.x if bnb is not None else other)),
-                               bnb.sc if bnb is not None else None, bnb.sh if bnb is not None else None,
-                               self._p(self.act(op.y)), int(op.relu), sp)
-                F.append(c)
-                I.append(c)
-            elif op.kind == "add":
-                c = self._call("rn_eltwise_add", op.y.numel, self.dtype, self._p(self.act(op.a)),
-                               self._p(self.act(op.b)), self._p(self.act(op.y)), int(op.relu), sp)
-                F.append(c)
-                I.append(c)
-            elif op.kind == "pool":
-                x, y = op.x, op.y
-                d = L.PoolDesc(dtype=self.dtype, n=x.n, h=x.h, w=x.w, c=x.cp, r=op.kernel[0], s=op.kernel[1],
-                               stride_h=op.stride[0], stride_w=op.stride[1], pad_h=op.pad[0], pad_w=op.pad[1],
-                               type=L.RN_POOL_MAX if op.type == "max" else L.RN_POOL_AVG,
-                               global_pool=int(op.global_pool))
-                L.check(self.lib.rn_pool_desc_init(L.C.byref(d)), "rn_pool_desc_init")
-                assert (d.p, d.q) == (y.h, y.w), (op.name, d.p, d.q, y.h, y.w)
-                op.desc = d
-                op.argmax = self.torch.zeros(max(y.rows * y.cp, 1), dtype=self.torch.uint8, device=self.device) \
-                    if op.type == "max" else None
-                if op.xf is not None:  # the producing BatchNorm+ReLU applied while loading
-                    c = self._call("rn_pool_fwd_x", L.C.byref(d), self._p(self.act(op.xf.x)), self._p(self.act(y)),
-                                   self._p(op.argmax), op.xf.sc, op.xf.sh, sp)
-                else:
-                    c = self._call("rn_pool_fwd", L.C.byref(d), self._p(self.act(x)), self._p(self.act(y)),
-                                   self._p(op.argmax), sp)
-                F.append(c)
-                I.append(c)
-            elif op.kind == "fc":
-                x, y = op.x, op.y
-                d = self._conv_desc(x.n, 1, 1, x.cp, x.c, op.nh, (1, 1), (1, 1), (0, 0))
-                op.desc = d
-                op.wk = self._zeros(op.nh * x.cp, self.tdtype)
-                op.wc = self._zeros(x.cp * _pad8(op.nh), self.tdtype)
-                if op not in self._wg_ops:  # (a GDRQ weight: both copies written by rn_weight_gdrq_pack)
-                    self._add_pack(op, d, op.wk, op.wc, sp)
-                bias = self._pp(op.bias) if op.bias else None
-                c = self._call("rn_conv_fwd", L.C.byref(d), self._p(self.act(x)), self._p(op.wk),
-                               self._p(self.act(y)), F32, None, bias, sp)
-                F.append(c)
-                I.append(c)
-            elif op.kind == "softmax":
-                x = op.x
-                # gradient of the logits is produced here (SoftmaxOutput's backward needs no head grad)
-                dl = self.grad_buf(x)
-                F.append(self._call("rn_softmax_output", self.dtype, x.n, x.c, x.cp, self._p(self.act(x)),
-                                    self._p(self.act(op.label)), self._p(self.act(op.y)), self._p(dl),
-                                    op.grad_scale, self._p(self.stats), sp))
-                I.append(self._call("rn_softmax_output", self.dtype, x.n, x.c, x.cp, self._p(self.act(x)),
-                                    self._p(self.act(op.label)), self._p(self.act(op.y)), None, op.grad_scale,
-                                    None, sp))
-            self._fwd_train.extend(F)
-            self._fwd_infer.extend(I)
-        self.stem_ws = self._zeros(stem_ws, self.torch.float32)
+        else:
+            I.append(self._call("rn_conv_fwd", L.C.byref(dfull), self._p(op.x8), self._p(op.wk),
+                                self._p(self.act(y)), self.dtype, None, None, sp))
+            F.append(self._conv_fwd_call(op, dfull, self._p(op.x8), None))
+
+    def _fwd_conv(self, op, F, I):
+        x, y = op.x, op.y
+        d = self._conv_desc(x.n, x.h, x.w, x.cp, x.c, y.c, op.kernel, op.stride, op.pad, op.groups)
+        assert (d.p, d.q) == (y.h, y.w), (op.name, d.p, d.q, y.h, y.w)
+        op.desc = d
+        op.wc = self._zeros(self.lib.rn_conv_pack_numel(L.C.byref(d), 1), self.tdtype)
+        wgdrq = op in self._wg_ops
+        if wgdrq and op.groups == 1 and not op.int8:
+            # (both compute copies written by rn_weight_gdrq_pack; their padding stays zero)
+            op.wk = self._zeros(self.lib.rn_conv_pack_numel(L.C.byref(d), 0), self.tdtype)
+        elif op.int8:
+            # forward copy: the int8 codes (KRSC); the data-gradient copy stays the
+            # fake-quantized values in the compute dtype (STE backward)
+            op.wk = None
+            op.wk8 = self.torch.zeros(int(self.lib.rn_conv_pack_numel(L.C.byref(d), 0)),
+                                      dtype=self.torch.int8, device=self.device)
+            if not self._wq_batch and not wgdrq:  # (batched: written by rn_weight_quant_pack)
+                self._add_pack(op, d, None, op.wc)
+                c_ = self._call("rn_conv_weight_pack_i8", L.C.byref(d), self._pp(op.weight),
+                                self._p(op.wunit), self._p(op.wk8), self._spv)
+                self.packs.append(c_)
+                self.unfused_packs.append(c_)
+        else:
+            op.wk = self._zeros(self.lib.rn_conv_pack_numel(L.C.byref(d), 0), self.tdtype)
+            self._add_pack(op, d, op.wk, op.wc)
+        res = self._p(self.act(op.res)) if op.res is not None else None
+        xin = self._p(self.act(op.xf.x)) if op.xf is not None else self._p(self.act(x))
+        I.append(self._conv_fwd_call(op, d, xin, res, stats=False))
+        # (allocates op.part / op.part_mm, which the BatchNorm bound after this conv reads)
+        F.append(self._conv_fwd_call(op, d, xin, res))
+
+    def _fwd_bn(self, op, F, I):
+        sp, wsp = self._spv, self._wsp
+        x, y = op.x, op.y
+        c = x.cp
+        op.buf = self._zeros(4 * c, self.torch.float32)
+        op.sm, op.si, op.sc, op.sh = [L.C.c_void_p(op.buf.data_ptr() + 4 * c * i) for i in range(4)]
+        gamma = self._pp(op.gamma)
+        # fused into the 1x1 consumers' loads or the quantizer's: coefficients only
+        yptr = None if op.apply_fused or op.apply_in_quant else self._p(self.act(y))
+        # (part_mm: allocated by _conv_fwd_call when the producing int8 conv, earlier in the plan, was bound)
+        if op.mm_src is not None and op.mm_src.part_mm is not None:
+            op.desc.xmm = op.mm_src.part_mm.data_ptr()
+            op.desc.xmm_blocks = op.mm_src.part_blocks
+        infer = self._call("rn_bn_fwd_infer", L.C.byref(op.desc), self._p(self.act(x)), yptr,
+                           gamma, self._pp(op.beta), self._ap(op.mean), self._ap(op.var), op.sc, op.sh, sp)
+        if op.use_global_stats:
+            F.append(infer)
+        elif op.part_src is not None:
+            s_ = op.part_src
+            F.append(self._call("rn_bn_fwd_train_part", L.C.byref(op.desc), self._p(s_.part), s_.part_blocks,
+                                s_.part_rows, s_.y.cp, self._p(self.act(x)), yptr, gamma, self._pp(op.beta),
+                                self._ap(op.mean), self._ap(op.var), op.sm, op.si, op.sc, op.sh, wsp, sp))
+        else:
+            F.append(self._call("rn_bn_fwd_train", L.C.byref(op.desc), self._p(self.act(x)), yptr, gamma,
+                                self._pp(op.beta), self._ap(op.mean),
+                                self._ap(op.var), op.sm, op.si, op.sc, op.sh, wsp, sp))
+        I.append(infer)
+
+    def _fwd_affine(self, op, F, I):
+        """y = [relu](x*scale + bias) with per-channel parameters copied into channel-padded
+        coefficient vectors each forward (set_params / SGD may change them)."""
+        sp = self._spv
+        x, y = op.x, op.y
+        c = x.cp
+        op.buf = self._zeros(4 * c, self.torch.float32)
+        if op.gamma is None:
+            op.buf[:x.c] = 1.0
+        op.sc, op.sh, op.zero, op.one = [L.C.c_void_p(op.buf.data_ptr() + 4 * c * i) for i in range(4)]
+        op.buf[3 * c:3 * c + x.c] = 1.0
+        op.desc = L.BNDesc(dtype=self.dtype, m=x.rows, c=c, c_real=x.c, eps=0.0, momentum=0.0,
+                           fix_gamma=int(op.gamma is None), relu=int(op.relu))
+        calls = [self._call("rn_cast", x.c, self._pp(nm), F32, dst, F32, sp)
+                 for nm, dst in ((op.gamma, op.sc), (op.beta, op.sh)) if nm is not None]
+        calls.append(self._call("rn_bn_apply", L.C.byref(op.desc), self._p(self.act(x)), self._p(self.act(y)),
+                                op.sc, op.sh, sp))
+        F.extend(calls)
+        I.extend(calls)
+
+    def _fwd_relu(self, op, F, I):
+        c = self._call("rn_eltwise_add", op.x.numel, self.dtype, self._p(self.act(op.x)), None,
+                       self._p(self.act(op.y)), 1, self._spv)
+        F.append(c)
+        I.append(c)
+
+    def _fwd_quant(self, op, F, I):
+        sp, qwsp = self._spv, self._qwsp
+        q = op.q
+        for o in (op, op.bn_peer):
+            if o is not None and o.emit_codes and o.codes is None:
+                # + the int8 codes and unit the consumers' int8 forward reads
+                o.codes = self.torch.zeros(o.x.numel, dtype=self.torch.int8, device=self.device)
+                o.unit = self._zeros(1, self.torch.float32)
+        # (codes_wgrad: codes only, the weight gradients multiply them)
+        vout = lambda o: None if o.codes_wgrad else self._p(self.act(o.y))  # noqa: E731
+        for lst, tr in ((F, 1), (I, 0)):
+            if op.bn_lead is not None:
+                pass  # written by its peer's call
+            elif op.bn_peer is not None:
+                bn, o2 = op.bn_src, op.bn_peer
+                lst.append(self._call("rn_quant_int8_fwd_codes_bn2", L.C.byref(bn.desc), self._p(self.act(bn.x)), bn.sc,
+                                      bn.sh, vout(op), self._p(op.codes), self._p(op.unit), self._ap(q["minmax"]),
+                                      q["ema"], q["nbits"], vout(o2), self._p(o2.codes), self._p(o2.unit),
+                                      self._ap(o2.q["minmax"]), o2.q["ema"], o2.q["nbits"], tr, self._qfirst, qwsp, sp))
+            elif op.bn_src is not None:
+                bn = op.bn_src
+                lst.append(self._call("rn_quant_int8_fwd_codes_bn", L.C.byref(bn.desc), self._p(self.act(bn.x)), bn.sc,
+                                      bn.sh, vout(op), self._p(op.codes), self._p(op.unit), self._ap(q["minmax"]), tr,
+                                      q["ema"], self._qfirst, q["nbits"], qwsp, sp))
+            elif op.emit_codes:
+                lst.append(self._call("rn_quant_int8_fwd_codes", self.dtype, op.x.numel, self._p(self.act(op.x)),
+                                      vout(op), self._p(op.codes), self._p(op.unit), self._ap(q["minmax"]), 0, tr,
+                                      q["ema"], self._qfirst, q["nbits"], qwsp, sp))
+            else:
+                lst.append(self._call("rn_quant_int8_fwd", self.dtype, op.x.numel, self._p(self.act(op.x)),
+                                      self._p(self.act(op.y)), self._ap(q["minmax"]), 0, tr, q["ema"],
+                                      self._qfirst, q["nbits"], qwsp, sp))
+
+    def _fwd_pact(self, op, F, I):
+        """The same in training and inference; gamma is read on the device from the flat master buffer, so
+        every step (and a replayed graph) sees the value the last update left. The values are always
+        written; with emit_codes also the int8 codes and the unit the consumers' int8 forward reads."""
+        op.unit = self._zeros(1, self.torch.float32)
+        op.codes = self.torch.zeros(op.x.numel, dtype=self.torch.int8, device=self.device) \
+            if op.emit_codes else None
+        c = self._call("rn_pact_fwd", self.dtype, op.x.numel, self._p(self.act(op.x)), self._pp(op.gamma),
+                       op.nbits, self._p(self.act(op.y)), self._p(op.codes), self._p(op.unit), self._spv)
+        F.append(c)
+        I.append(c)
+
+    def _fwd_gdrq(self, op, F, I):
+        """alpha is read (and, in training without fix_alpha, first updated) on the device in the aux buffer:
+        no host synchronisation, a replayed graph sees the current value. Inference never writes it. The
+        values are always written; with emit_codes also the signed int8 codes and the unit."""
+        x = op.x
+        op.unit = self._zeros(1, self.torch.float32)
+        op.codes = self.torch.zeros(x.numel, dtype=self.torch.int8, device=self.device) \
+            if op.emit_codes else None
+        if not op.fix_alpha and self._gdrq_ws is None:  # (one buffer, made by the first op that needs it)
+            nmax = max(o.x.numel for o in self.plan.ops if o.kind == "gdrq" and not o.fix_alpha)
+            self._gdrq_ws = self._zeros(int(self.lib.rn_gdrq_ws_bytes(nmax)) // 4, self.torch.float32)
+        for lst, upd in ((F, int(not op.fix_alpha)), (I, 0)):
+            lst.append(self._call("rn_gdrq_fwd", self.dtype, x.numel, x.rows * x.c, self._p(self.act(x)),
+                                  self._ap(op.alpha), op.nbits, upd, op.ktimes, op.lamda, self._p(self.act(op.y)),
+                                  self._p(op.codes), self._p(op.unit),
+                                  self._p(self._gdrq_ws) if upd else None, self._spv))
+
+    def _fwd_add(self, op, F, I):
+        if op.bn_a is not None:  # the BatchNorms of the post-activation unit tail applied inside the add
+            bna, bnb = op.bn_a, op.bn_b
+            other = op.b if op.bn_a_key == "a" else op.a
+            c = self._call("rn_bn_apply_add", L.C.byref(bna.desc), self._p(self.act(bna.x)), bna.sc, bna.sh,
+                           self._p(self.act(bnb.x if bnb is not None else other)), bnb.sc if bnb is not None else None,
+                           bnb.sh if bnb is not None else None, self._p(self.act(op.y)), int(op.relu), self._spv)
+        else:
+            c = self._call("rn_eltwise_add", op.y.numel, self.dtype, self._p(self.act(op.a)),
+                           self._p(self.act(op.b)), self._p(self.act(op.y)), int(op.relu), self._spv)
+        F.append(c)
+        I.append(c)
+
+    def _fwd_pool(self, op, F, I):
+        x, y = op.x, op.y
+        d = L.PoolDesc(dtype=self.dtype, n=x.n, h=x.h, w=x.w, c=x.cp, r=op.kernel[0], s=op.kernel[1],
+                       stride_h=op.stride[0], stride_w=op.stride[1], pad_h=op.pad[0], pad_w=op.pad[1],
+                       type=L.RN_POOL_MAX if op.type == "max" else L.RN_POOL_AVG, global_pool=int(op.global_pool))
+        L.check(self.lib.rn_pool_desc_init(L.C.byref(d)), "rn_pool_desc_init")
+        assert (d.p, d.q) == (y.h, y.w), (op.name, d.p, d.q, y.h, y.w)
+        op.desc = d
+        op.argmax = self.torch.zeros(max(y.rows * y.cp, 1), dtype=self.torch.uint8, device=self.device) \
+            if op.type == "max" else None
+        if op.xf is not None:  # the producing BatchNorm+ReLU applied while loading
+            c = self._call("rn_pool_fwd_x", L.C.byref(d), self._p(self.act(op.xf.x)), self._p(self.act(y)),
+                           self._p(op.argmax), op.xf.sc, op.xf.sh, self._spv)
+        else:
+            c = self._call("rn_pool_fwd", L.C.byref(d), self._p(self.act(x)), self._p(self.act(y)),
+                           self._p(op.argmax), self._spv)
+        F.append(c)
+        I.append(c)
+
+    def _fwd_fc(self, op, F, I):
+        x, y = op.x, op.y
+        d = self._conv_desc(x.n, 1, 1, x.cp, x.c, op.nh, (1, 1), (1, 1), (0, 0))
+        op.desc = d
+        op.wk = self._zeros(op.nh * x.cp, self.tdtype)
+        op.wc = self._zeros(x.cp * _pad8(op.nh), self.tdtype)
+        if op not in self._wg_ops:  # (a GDRQ weight: both copies written by rn_weight_gdrq_pack)
+            self._add_pack(op, d, op.wk, op.wc)
+        bias = self._pp(op.bias) if op.bias else None
+        c = self._call("rn_conv_fwd", L.C.byref(d), self._p(self.act(x)), self._p(op.wk),
+                       self._p(self.act(y)), F32, None, bias, self._spv)
+        F.append(c)
+        I.append(c)
+
+    def _fwd_softmax(self, op, F, I):
+        x = op.x
+        # gradient of the logits is produced here (SoftmaxOutput's backward needs no head grad)
+        dl = self.grad_buf(x)
+        F.append(self._call("rn_softmax_output", self.dtype, x.n, x.c, x.cp, self._p(self.act(x)),
+                            self._p(self.act(op.label)), self._p(self.act(op.y)), self._p(dl),
+                            op.grad_scale, self._p(self.stats), self._spv))
+        I.append(self._call("rn_softmax_output", self.dtype, x.n, x.c, x.cp, self._p(self.act(x)),
+                            self._p(self.act(op.label)), self._p(self.act(op.y)), None, op.grad_scale, None, self._spv))
+
+    def _wquant_shape(self, op):
+        """(k, c_real, r*s) of a quantized weight."""
+        shape = self.plan.param_shape(op.weight)
+        return shape[0], shape[1], int(np.prod(shape[2:])) if len(shape) > 2 else 1
+
+    def _bind_weight_packs(self):
+        """The three batched tails, bound after the forward walk has met every weight: rn_weight_quant_pack and
+        rn_weight_gdrq_pack go to the front of the pack lists (the stem's and the grouped layers' packs read their
+        fake-quantized copies), rn_conv_weight_pack_multi to the end."""
+        sp = self._spv
         if self._wq_ops:
             items = []
             for op in self._wq_ops:
-                shape = self.plan.param_shape(op.weight)
-                k, creal = shape[0], shape[1]
-                rs = int(np.prod(shape[2:])) if len(shape) > 2 else 1
-                i8 = getattr(op, "int8", False)
+                k, creal, rs = self._wquant_shape(op)
+                i8 = op.int8
                 d = op.desc if i8 else None
                 assert not i8 or (d.groups <= 1 and d.k == k and d.c_real == creal and d.r * d.s == rs)
                 items.append(L.WQuantItem(
                     master=self._pp(op.weight).value, qw=op.qw.data_ptr(),
                     unit=op.wunit.data_ptr() if i8 else None, minmax=self._ap(op.qweight["minmax"]).value,
-                    w_codes=op.wk8.data_ptr() if i8 else None, w_crsk=op.wc.data_ptr() if i8 else None,
-                    k=k, rs=rs, c_real=creal, c=d.c if i8 else creal, k_pad=d.k_pad if i8 else k,
-                    nbits=int(op.qweight["nbits"])))
+                    w_codes=op.wk8.data_ptr() if i8 else None, w_crsk=op.wc.data_ptr() if i8 else None, k=k, rs=rs,
+                    c_real=creal, c=d.c if i8 else creal, k_pad=d.k_pad if i8 else k, nbits=int(op.qweight["nbits"])))
             arr = (L.WQuantItem * len(items))(*items)
             self._wq_items = self.torch.frombuffer(bytearray(arr), dtype=self.torch.uint8).to(self.device)
-            c_ = self._call("rn_weight_quant_pack", self._p(self._wq_items), len(items), self.dtype, qwsp, sp)
+            c_ = self._call("rn_weight_quant_pack", self._p(self._wq_items), len(items), self.dtype, self._qwsp, sp)
             self.packs.insert(0, c_)
             self.unfused_packs.insert(0, c_)
         if self._wg_ops:
@@ -1452,10 +804,8 @@ class Executor:
             # (the stem's and the grouped layers'): thresholds, units, the copies of the dense layers
             items = []
             for op in self._wg_ops:
-                shape = self.plan.param_shape(op.weight)
-                k, creal = shape[0], shape[1]
-                rs = int(np.prod(shape[2:])) if len(shape) > 2 else 1
-                i8 = getattr(op, "int8", False)
+                k, creal, rs = self._wquant_shape(op)
+                i8 = op.int8
                 dense = op.kind == "fc" or (op.kind == "conv" and op.groups == 1)
                 d = op.desc if dense else None
                 assert not dense or (d.k == k and d.c_real == creal and d.r * d.s == rs), op.name
@@ -1463,11 +813,10 @@ class Executor:
                 items.append(L.WGdrqItem(
                     master=self._pp(op.weight).value, qw=op.qw.data_ptr(),
                     unit=op.wunit.data_ptr() if i8 else None, alpha=self._ap(q["alpha"]).value,
-                    w_codes=op.wk8.data_ptr() if i8 else None,
-                    w_krsc=op.wk.data_ptr() if dense and not i8 else None,
-                    w_crsk=op.wc.data_ptr() if dense else None,
-                    k=k, rs=rs, c_real=creal, c=d.c if dense else creal, k_pad=d.k_pad if dense else k,
-                    nbits=int(q["nbits"]), fix_alpha=int(q["fix_alpha"]), ktimes=float(q["ktimes"])))
+                    w_codes=op.wk8.data_ptr() if i8 else None, w_krsc=op.wk.data_ptr() if dense and not i8 else None,
+                    w_crsk=op.wc.data_ptr() if dense else None, k=k, rs=rs, c_real=creal, c=d.c if dense else creal,
+                    k_pad=d.k_pad if dense else k, nbits=int(q["nbits"]), fix_alpha=int(q["fix_alpha"]),
+                    ktimes=float(q["ktimes"])))
             arr = (L.WGdrqItem * len(items))(*items)
             self._wg_items = self.torch.frombuffer(bytearray(arr), dtype=self.torch.uint8).to(self.device)
             self._wg_ws = self._zeros(int(self.lib.rn_weight_gdrq_ws_bytes(len(items))) // 4, self.torch.float32)
@@ -1492,7 +841,7 @@ class Executor:
         variant on the 128/256-column tiles only)?"""
         if op.kind != "conv" or self.lib is None:
             return False
-        if getattr(op, "int8", False) and mode == 0:  # the int8 forward's tile (its dgrad is the bf16 one)
+        if op.int8 and mode == 0:  # the int8 forward's tile (its dgrad is the bf16 one)
             x, y = op.x, op.y
             d = self._conv_desc(x.n, x.h, x.w, x.cp, x.c, y.c, op.kernel, op.stride, op.pad, op.groups)
             mc = min_cols if min_cols is not None else 128
@@ -1506,9 +855,8 @@ class Executor:
     def _grouped_fuse(self, op, mode):
         """Does grouped conv `op` carry the BN fusion in its forward (mode 0: the statistics epilogue of
         the block-diagonal 256x64 tile) / data gradient (mode 1: the BN-backward reduction of that tile
-        or of the direct kernel, rn_conv_bwd_data_bnred)? RN_GROUPED_BN_FUSION=0: neither (A/B)."""
-        if op.kind != "conv" or op.groups <= 1 or self.lib is None or self.dtype != L.RN_BF16 or \
-                os.environ.get("RN_GROUPED_BN_FUSION", "1") != "1":
+        or of the direct kernel, rn_conv_bwd_data_bnred)?"""
+        if op.kind != "conv" or op.groups <= 1 or self.lib is None or self.dtype != L.RN_BF16:
             return False
         x, y = op.x, op.y
         d = self._conv_desc(x.n, x.h, x.w, x.cp, x.c, y.c, op.kernel, op.stride, op.pad, op.groups)
@@ -1526,20 +874,21 @@ class Executor:
         d = self._conv_desc(x.n, x.h, x.w, x.cp, x.c, y.c, op.kernel, op.stride, op.pad, op.groups)
         return d.grouped_direct == 2
 
-    def _conv_fwd_call(self, op, d, xptr, res, sp, stats=True):
+    def _conv_fwd_call(self, op, d, xptr, res, stats=True):
         """Conv forward; emits the next BatchNorm's statistics when one consumes y (training), and
         applies the producing BatchNorm+ReLU on load when that BN is fused (op.xf)."""
+        sp = self._spv
         y = self._p(self.act(op.y))
-        if getattr(op, "int8", False):
+        if op.int8:
             part = None
             if stats and op.bnstats:
-                if getattr(op, "part", None) is None:
+                if op.part is None:
                     op.part_rows = int(self.lib.rn_conv_bn_part_rows(L.C.byref(d), 2))
                     op.part_blocks = -(-op.y.rows // op.part_rows)
                     op.part = self._zeros(op.part_blocks * 3 * op.y.cp, self.torch.float32)
                 part = self._p(op.part)
                 if op.want_mm:  # + per-block max / min of y for the quantizers that read bn(y)
-                    if getattr(op, "part_mm", None) is None:
+                    if op.part_mm is None:
                         op.part_mm = self._zeros(op.part_blocks * op.y.cp, self.torch.float32)
                     sign = self._pp(op.mm_gamma) if op.mm_gamma else None
                     return self._call("rn_conv_fwd_i8_mm", L.C.byref(d), self._p(op.qsrc.codes), self._p(op.wk8),
@@ -1547,11 +896,10 @@ class Executor:
                                       self._p(op.part_mm), sign, sp)
             return self._call("rn_conv_fwd_i8", L.C.byref(d), self._p(op.qsrc.codes), self._p(op.wk8), y,
                               self.dtype, res, self._p(op.qsrc.unit), self._p(op.wunit), part, sp)
-        xf = getattr(op, "xf", None)
-        sc, sh = (xf.sc, xf.sh) if xf is not None else (None, None)
+        sc, sh = (op.xf.sc, op.xf.sh) if op.xf is not None else (None, None)
         part = None
         if stats and op.bnstats:
-            if getattr(op, "part", None) is None:
+            if op.part is None:
                 op.part_blocks = int(self.lib.rn_conv_bnstats_blocks(L.C.byref(d)))
                 op.part_rows = int(self.lib.rn_conv_bn_part_rows(L.C.byref(d), 0))
                 op.part = self._zeros(op.part_blocks * 3 * op.y.cp, self.torch.float32)
@@ -1583,14 +931,14 @@ class Executor:
             return 1
         return nch
 
-    def _weight_source(self, op, qwsp, sp):
+    def _weight_source(self, op):
         """Quantization_int8 on a weight (int8_api.py:131-132): the compute copies are packed from a
         fake-quantized fp32 copy of the master, refreshed with every repack; the STE passes the
         gradient to the master unchanged."""
         q = op.qweight
         n = int(np.prod(self.plan.param_shape(op.weight)))
         op.qw = self._zeros(n, self.torch.float32)
-        if getattr(op, "int8", False):  # also keeps the unit for the int8 codes of the forward copy
+        if op.int8:  # also keeps the unit for the int8 codes of the forward copy
             op.wunit = self._zeros(1, self.torch.float32)
         if q.get("family") == "gdrq":
             # a GDRQ weight (core/operator/GDRQ.py: alpha = ktimes * mean|w| unless fix_alpha, clip, round; plain
@@ -1602,23 +950,24 @@ class Executor:
             # the fake-quantized copy, and for the int8 convs their codes and data-gradient copy too
             self._wq_ops.append(op)
             return self._p(op.qw)
-        if getattr(op, "int8", False):
+        if op.int8:
             c = self._call("rn_quant_int8_fwd_codes", F32, n, self._pp(op.weight), self._p(op.qw), None,
-                           self._p(op.wunit), self._ap(q["minmax"]), 1, 1, q["ema"], 0, q["nbits"], qwsp, sp)
+                           self._p(op.wunit), self._ap(q["minmax"]), 1, 1, q["ema"], 0, q["nbits"], self._qwsp,
+                           self._spv)
         else:
             c = self._call("rn_quant_int8_fwd", F32, n, self._pp(op.weight), self._p(op.qw),
-                           self._ap(q["minmax"]), 1, 1, q["ema"], 0, q["nbits"], qwsp, sp)
+                           self._ap(q["minmax"]), 1, 1, q["ema"], 0, q["nbits"], self._qwsp, self._spv)
         self.packs.append(c)
         self.unfused_packs.append(c)
         return self._p(op.qw)
 
-    def _add_pack(self, op, d, wk, wc, sp):
+    def _add_pack(self, op, d, wk, wc):
         """Compute copies of op's weight. Dense weights packed straight from the master are
         rewritten by the fused SGD kernel (rn_sgd_mom_update_pack); the bind-time pack below also
         writes their zero padding, which that kernel never touches."""
-        c = self._call("rn_conv_weight_pack", L.C.byref(d), op.wsrc, self._p(wk), self._p(wc), sp)
+        c = self._call("rn_conv_weight_pack", L.C.byref(d), op.wsrc, self._p(wk), self._p(wc), self._spv)
         self.packs.append(c)
-        if d.groups == 1 and not getattr(op, "qweight", None) and self.fuse_packs:
+        if d.groups == 1 and not op.qweight:
             self.fused_packs[op.weight] = (wk.data_ptr() if wk is not None else 0,
                                            wc.data_ptr() if wc is not None else 0,
                                            d.k, d.r * d.s, d.c_real, d.c, d.k_pad)
@@ -1628,12 +977,12 @@ class Executor:
             self.unfused_packs.append(c)
 
     # ------------------------------------------------------------------ backward
-    def _wgrad_call(self, d, x, dy, dw, sp):
+    def _wgrad_call(self, d, x, dy, dw):
         """rn_conv_bwd_filter, through the split-M slab workspace where the kernel uses one."""
         if self.wgrad_ws is not None and int(self.lib.rn_conv_wgrad_ws_bytes(L.C.byref(d))) > 0:
             return self._call("rn_conv_bwd_filter_ws", L.C.byref(d), x, dy, dw, self._p(self.wgrad_ws),
-                              self.wgrad_ws_bytes, sp)
-        return self._call("rn_conv_bwd_filter", L.C.byref(d), x, dy, dw, sp)
+                              self.wgrad_ws_bytes, self._spv)
+        return self._call("rn_conv_bwd_filter", L.C.byref(d), x, dy, dw, self._spv)
 
     # the recomputed BN backward's size gate: measured cold per layer (DESIGN.md), the recomputed chain wins from
     # 98 MiB up on both layer classes (stage 1's from 25 MiB) and loses or ties below (stage 2's class at 49 MiB: 2 %
@@ -1676,81 +1025,103 @@ class Executor:
         outs = {id(t) for t in self.plan.outputs}
         groups = {}
         for bn in ops:
-            if bn.kind != "bn" or not bn.relu or id(bn.y) in outs or getattr(bn, "apply_fused", False):
+            if bn.kind != "bn" or not bn.relu or id(bn.y) in outs or bn.apply_fused:
                 continue
             qs = qreaders.get(id(bn.y), [])
             if qs and len(qs) == readers.get(id(bn.y)) and len(qs) <= 2:
                 groups[id(bn)] = (bn, qs)
         return groups
 
-    def _quant_folds(self):
-        """{id(quant op): bn op} over _quant_groups (the quantizers whose backward folds into a BN's)."""
-        return {id(q): bn for bn, qs in self._quant_groups().values() for q in qs}
-
     def _build_backward(self):
-        plan = self.plan
-        sp = self._sp()
+        """The setup passes, then one _bwd_<kind>(op, dy, gs) per op in reverse plan order, dy the op's output
+        gradient and gs the gradient routing."""
         gs = _GradState(self)
+        self.param_done_at = {}  # param -> index in self._bwd after which its grad is final
+        self._gw = {}  # id(tensor) -> last writer of its gradient buffer: ("dgrad", call index, conv op)
+        self._pact_ws = None  # rn_pact_bwd's block partials: one buffer for every PACT (compute stream, plan order)
+        self._bind_quant_folds()
+        self._read_bn_bwd_modes()
+        self._size_wgrad_ws()  # (before every binder: they pass the slab, or test for it)
+        self._bwd_stem_clip_masks()  # (first in self._bwd: depends on the forward only, SIDE_PRE_CALLS)
+        for op in reversed(self.plan.ops):
+            if op.kind == "softmax":
+                gs.has_value.add(id(op.x))  # dlogits written by the forward softmax call
+                continue
+            dy = self._qpair_dy(op, gs) if op.kind == "bn" and op.qpair else gs.read(op.y)
+            if dy is not None:
+                getattr(self, "_bwd_" + op.kind)(op, dy, gs)
+            dy = None  # (a recomputed BatchNorm releases its output gradient's buffer: no name here keeps it)
+        self._gw = {}  # (the writer records hold gradient tensors and serve only while the plan is bound)
+
+    def _bind_quant_folds(self):
+        """The quantizers whose backward folds into a BatchNorm's (_quant_groups): self._folds {id(quant op): bn},
+        and a single quantizer's threshold into its BN's descriptor -- which the forward calls already hold by
+        reference."""
         groups = self._quant_groups()
-        folds = {id(q): bn for bn, qs in groups.values() for q in qs}
-        for op in plan.ops:
+        self._folds = {id(q): bn for bn, qs in groups.values() for q in qs}
+        for op in self.plan.ops:
             if op.kind == "bn":
                 op.qpair = False
                 op.qorder = []  # the folded quantizers in backward order (their gradients' pending order)
+                op.pre_part = None  # set by the residual add's fused ReLU backward (this build)
+                op.recomputed = False  # its backward applied by a recomputed dgrad (rn_conv_bwd_data_bnapply)
         for bn, qs in groups.values():
             if len(qs) == 1:
                 bn.desc.clip = self._ap(qs[0].q["minmax"]).value  # (the threshold the forward just updated)
             else:
-                bn.qpair = True  # clip / clip2 / dy2 set where its backward is bound
-        wsp = self._p(self.ws)
-        self.param_done_at = {}  # param -> index in self._bwd after which its grad is final
-        self._gw = {}  # id(tensor) -> last writer of its gradient buffer: ("dgrad", call index, conv op)
-        self._pact_ws = None  # rn_pact_bwd's block partials: one buffer for every PACT (compute stream, plan order)
+                bn.qpair = True  # clip / clip2 / dy2 set where its backward is bound (_qpair_dy)
+
+    def _read_bn_bwd_modes(self):
         # default on where the dgrad runs the 256-row tile (see RN_BN_EPILOGUE_STATS; =2: every dgrad)
-        for op in plan.ops:
-            if op.kind == "bn":
-                op.pre_part = None  # set by the residual add's fused ReLU backward (this build)
-                op.recomputed = False  # its backward applied by a recomputed dgrad (rn_conv_bwd_data_bnapply)
-        bwd_fusion = os.environ.get("RN_BN_BWD_FUSION", "1") in ("1", "2")
-        bwd_all = os.environ.get("RN_BN_BWD_FUSION", "1") == "2"
+        self._bwd_fusion = os.environ.get("RN_BN_BWD_FUSION", "1") in ("1", "2")
+        self._bwd_all = os.environ.get("RN_BN_BWD_FUSION", "1") == "2"
         # the BN backward applied by a recomputed streamed dgrad (rn_conv_bwd_data_bnapply, _bn_recompute_ok):
         # RN_BN_BWD_RECOMPUTE=0 keeps the stored gradient everywhere, 1 recomputes every such layer whatever its
         # size, unset those of at least RECOMPUTE_MIN_BYTES (DESIGN.md has the measurements)
         rmode = os.environ.get("RN_BN_BWD_RECOMPUTE", "")
         if rmode not in ("", "0", "1"):
             raise L.RNError("RN_BN_BWD_RECOMPUTE=%r: 0, 1 or unset" % rmode)
-        recompute_min_bytes = {"": self.RECOMPUTE_MIN_BYTES, "0": None, "1": 0}[rmode]
+        self._recompute_min_bytes = {"": self.RECOMPUTE_MIN_BYTES, "0": None, "1": 0}[rmode]
         # (removed in round 6, measured neutral, its kernel kept and kernel-tested by tests/test_kernels_gpu.py::
         # test_dgrad_quant_pair_clip_fold: a quantizer pair's clips folded into the later data gradient,
         # RN_QUANT_PAIR_FUSION -- rn_conv_bwd_data_bnred_clip2; C5 22.68 / 22.69 vs 22.69 / 22.68 ms)
-        # one workspace for the weight gradients' split-M partial tiles (rn_conv_bwd_filter_ws),
-        # sized for the largest layer. Shared safely because every call using it is a weight-gradient
-        # call, and those all run in plan order on ONE stream (the side stream when it is on:
-        # _route_wgrads enforces this)
-        self.wgrad_ws, self.wgrad_ws_bytes = None, 0
-        if os.environ.get("RN_WGRAD_SLAB", "1") == "1":
-            def need_now():
-                need = [int(self.lib.rn_conv_wgrad_ws_bytes(L.C.byref(op.desc))) for op in plan.ops
-                        if op.kind in ("conv", "fc") and getattr(op, "desc", None) is not None]
-                # (the stem's weight gradient; it needs a slab only in the deterministic mode)
-                need += [int(self.lib.rn_conv_wgrad_ws_bytes(L.C.byref(op.dfull))) for op in plan.ops
-                         if op.kind == "stem" and not op.p4]
-                need += [int(self.lib.rn_stem_clip_wgrad_ws_bytes(L.C.byref(op.dfull))) for op in plan.ops
-                         if op.kind == "stem" and self._stem_clip_mask(op)]
-                need += [int(self.lib.rn_conv_wgrad_i8_ws_bytes(L.C.byref(op.desc))) for op in plan.ops
-                         if op.kind == "conv" and getattr(op, "qsrc", None) is not None and op.qsrc.codes_wgrad]
-                return max(need + [0])
-            # sized for both weight-gradient grids: the overlapped one (part of the chip) and the whole
-            # chip, which a serialised step (side_enabled False: bench.py's calibration) runs with
-            overlapped = os.environ.get("RN_WGRAD_STREAM", "1") == "1"
-            self.wgrad_ws_bytes = need_now()
-            if overlapped:
-                L.set_wgrad_split(False)
-                self.wgrad_ws_bytes = max(self.wgrad_ws_bytes, need_now())
-                L.set_wgrad_split(True, self.wgrad_split_pct)
-            if self.wgrad_ws_bytes > 0:
-                self.wgrad_ws = self._zeros(self.wgrad_ws_bytes // 4, self.torch.float32)
-        for op in plan.ops:
+
+    def _wgrad_ws_need(self):
+        """Bytes of split-M slab workspace the largest weight gradient needs under the current grid split."""
+        ops = self.plan.ops
+        need = [int(self.lib.rn_conv_wgrad_ws_bytes(L.C.byref(op.desc))) for op in ops
+                if op.kind in ("conv", "fc") and op.desc is not None]
+        # (the stem's weight gradient; it needs a slab only in the deterministic mode)
+        need += [int(self.lib.rn_conv_wgrad_ws_bytes(L.C.byref(op.dfull))) for op in ops
+                 if op.kind == "stem" and not op.p4]
+        need += [int(self.lib.rn_stem_clip_wgrad_ws_bytes(L.C.byref(op.dfull))) for op in ops
+                 if op.kind == "stem" and self._stem_clip_mask(op)]
+        need += [int(self.lib.rn_conv_wgrad_i8_ws_bytes(L.C.byref(op.desc))) for op in ops
+                 if op.kind == "conv" and op.qsrc is not None and op.qsrc.codes_wgrad]
+        return max(need + [0])
+
+    def _size_wgrad_ws(self):
+        """One workspace for the weight gradients' split-M partial tiles (rn_conv_bwd_filter_ws),
+        sized for the largest layer. Shared safely because every call using it is a weight-gradient
+        call, and those all run in plan order on ONE stream (the side stream when it is on:
+        _route_wgrads enforces this). None where no layer needs a slab."""
+        self.wgrad_ws = None
+        # sized for both weight-gradient grids: the overlapped one (part of the chip) and the whole
+        # chip, which a serialised step (side_enabled False: bench.py's calibration) runs with
+        self.wgrad_ws_bytes = self._wgrad_ws_need()
+        if os.environ.get("RN_WGRAD_STREAM", "1") == "1":
+            L.set_wgrad_split(False)
+            self.wgrad_ws_bytes = max(self.wgrad_ws_bytes, self._wgrad_ws_need())
+            L.set_wgrad_split(True, self.wgrad_split_pct)
+        if self.wgrad_ws_bytes > 0:
+            self.wgrad_ws = self._zeros(self.wgrad_ws_bytes // 4, self.torch.float32)
+
+    def _wgrad_ws_args(self, use=True):
+        """(workspace pointer, bytes) operands of the weight gradients that take the slab as an option."""
+        return (self._p(self.wgrad_ws), self.wgrad_ws_bytes) if use and self.wgrad_ws is not None else (None, 0)
+
+    def _bwd_stem_clip_masks(self):
+        for op in self.plan.ops:
             if op.kind == "stem" and self._stem_clip_mask(op):
                 # the int8 stem's clip masks into the NHWC-8 image's free channels (rn_stem_clip_mask),
                 # first on the weight-gradient stream: its clip gradient then rides in the stem's weight
@@ -1759,313 +1130,308 @@ class Executor:
                 op.clip_ext = self._zeros(op.dfull.k * op.dfull.r * op.dfull.s * 2 * op.dfull.c_real,
                                           self.torch.float32)
                 self._bwd.append(self._call("rn_stem_clip_mask", L.C.byref(op.dfull), self._in_ptr, sc, sh,
-                                            self._ap(op.quant["minmax"]), self._p(op.x8), sp))
-        for op in reversed(plan.ops):
-            if op.kind == "softmax":
-                gs.has_value.add(id(op.x))  # dlogits written by the forward softmax call
-                continue
-            if op.kind == "bn" and op.qpair:
-                # two folded quantizers: their output gradients stay separate (dy, rn_bn_desc.dy2)
-                assert id(op.y) not in gs.has_value
-                pend = gs.pending.pop(id(op.y), [])
-                if not pend:
-                    continue
-                dy = pend[0]
-                op.desc.clip = self._ap(op.qorder[0].q["minmax"]).value
-                if len(pend) == 2:
-                    op.desc.clip2 = self._ap(op.qorder[1].q["minmax"]).value
-                    op.desc.dy2 = self._p(pend[1]).value
+                                            self._ap(op.quant["minmax"]), self._p(op.x8), self._spv))
+
+    def _qpair_dy(self, op, gs):
+        """The output gradient of a BatchNorm with two folded quantizers: their gradients stay separate (dy,
+        rn_bn_desc.dy2), the thresholds go into the descriptor the forward calls hold by reference."""
+        assert id(op.y) not in gs.has_value
+        pend = gs.pending.pop(id(op.y), [])
+        if not pend:
+            return None
+        op.desc.clip = self._ap(op.qorder[0].q["minmax"]).value
+        if len(pend) == 2:
+            op.desc.clip2 = self._ap(op.qorder[1].q["minmax"]).value
+            op.desc.dy2 = self._p(pend[1]).value
+        return pend[0]
+
+    def _bwd_fc(self, op, dy, gs):
+        x = op.x
+        self._bwd.append(self._wgrad_call(op.desc, self._p(self.act(x)), self._p(dy), self._gp(op.weight)))
+        if op.bias:
+            self._bwd.append(self._call("rn_col_sum", self.dtype, x.n, op.nh, _pad8(op.nh), self._p(dy),
+                                        self._gp(op.bias), 0, self._spv))
+            self.param_done_at[op.bias] = len(self._bwd)
+        self.param_done_at[op.weight] = len(self._bwd)
+        if x.needs_grad:
+            out, add = gs.contribute(x)
+            self._bwd.append(self._call("rn_conv_bwd_data", L.C.byref(op.desc), self._p(dy), self._p(op.wc),
+                                        self._p(out), self._p(add), self._spv))
+
+    def _bwd_conv(self, op, dy, gs):
+        x, sp = op.x, self._spv
+        if op.xf is not None:  # input = BN+ReLU(bn input), applied on load
+            ws = int(self.lib.rn_conv_wgrad_ws_bytes(L.C.byref(op.desc))) > 0
+            self._bwd.append(self._call("rn_conv_bwd_filter_x", L.C.byref(op.desc), self._p(self.act(op.xf.x)),
+                                        self._p(dy), self._gp(op.weight), op.xf.sc, op.xf.sh,
+                                        *self._wgrad_ws_args(ws), sp))
+        elif op.qsrc is not None and op.qsrc.codes_wgrad:  # the input's codes, x its unit
+            q = op.qsrc
+            self._bwd.append(self._call("rn_conv_bwd_filter_i8", L.C.byref(op.desc), self._p(q.codes), self._p(q.unit),
+                                        self._p(dy), self._gp(op.weight), *self._wgrad_ws_args(), sp))
+        else:
+            self._bwd.append(self._wgrad_call(op.desc, self._p(self.act(x)), self._p(dy), self._gp(op.weight)))
+        self.param_done_at[op.weight] = len(self._bwd)
+        if x.needs_grad:
+            out, add = gs.contribute(x)
+            self._bwd.append(self._call("rn_conv_bwd_data", L.C.byref(op.desc), self._p(dy), self._p(op.wc),
+                                        self._p(out), self._p(add), sp))
+            self._gw[id(x)] = ("dgrad", len(self._bwd) - 1, op, dy, out, add)
+        if op.res is not None and op.res.needs_grad:
+            gs.alias(op.res, dy)
+
+    def _bwd_stem_chunked(self, op, dy, nch):
+        """The stem BN's dx (= dy here) per image chunk, each chunk's weight gradient (side
+        stream) starting as soon as its rows are applied: only the last chunk's wgrad
+        stays on the step's critical path (rn_bn_bwd then reduces + finalizes only)."""
+        sp = self._spv
+        bname, bfn, bargs = self._bwd[-1]
+        if bname == "rn_bn_bwd":
+            self._bwd[-1] = (bname, bfn, bargs[:3] + (None,) + bargs[4:])
+        else:  # rn_bn_bwd_part: finalize only, its coefficients where rn_bn_bwd_apply_rows reads
+            # them (after the reduction partials of rn_bn_bwd's own layout in the workspace)
+            bd, part, nrb, xp_, dyp_, dxp_, _, gp_, smp, sip, scp, shp, dgp, dbp, wsp_, _ = bargs
+            coef = wsp_.value + 4 * 2 * int(self.lib.rn_bn_reduce_blocks(bd)) * bd._obj.c
+            self._bwd[-1] = self._call("rn_bn_bwd_finalize", bd, part, nrb, gp_, smp, sip, dgp, dbp,
+                                       L.C.c_void_p((coef + 15) // 16 * 16), sp)
+            bargs = (bd, xp_, dyp_, dxp_, None, gp_, smp, sip, scp, shp, dgp, dbp, wsp_, sp)
+        d = op.dfull
+        nc = d.n // nch
+        rows = nc * d.p * d.q
+        for i in range(nch):
+            dc = self._conv_desc(nc, d.h, d.w, d.c, d.c_real, d.k, (d.r, d.s), (d.stride_h, d.stride_w),
+                                 (d.pad_h, d.pad_w))
+            self._descs.append(dc)
+            self._bwd.append(self._call("rn_bn_bwd_apply_rows", bargs[0], bargs[1], bargs[2], bargs[3],
+                                        None, bargs[8], bargs[9], bargs[12], i * rows, rows, sp))
+            dyc = L.C.c_void_p(self._p(dy).value + i * rows * d.k_pad * 2)
+            if op.p4:
+                hp, wp = op.p4
+                self._bwd.append(self._call("rn_stem_conv_wgrad_p4", L.C.byref(dc),
+                    L.C.c_void_p(op.x8.data_ptr() + i * nc * hp * wp * 4 * 2), dyc, self._gp(op.weight), hp, wp, sp))
+            else:  # the int8 stem: NHWC-8 chunks, clip masks in channels c_real..
+                self._bwd.append(self._call("rn_stem_clip_wgrad_chunk", L.C.byref(dc),
+                    L.C.c_void_p(op.x8.data_ptr() + i * nc * d.h * d.w * 8 * 2), dyc, self._gp(op.weight),
+                    self._p(op.clip_ext), *self._wgrad_ws_args(), int(i == 0), int(i == nch - 1), sp))
+
+    def _bwd_stem(self, op, dy, gs):
+        sp = self._spv
+        nch = self._stem_chunks(op, dy)
+        if nch > 1:
+            self._bwd_stem_chunked(op, dy, nch)
+        elif op.p4:
+            self._bwd.append(self._call("rn_stem_conv_wgrad_p4", L.C.byref(op.dfull), self._p(op.x8),
+                                        self._p(dy), self._gp(op.weight), op.p4[0], op.p4[1], sp))
+        elif self._stem_clip_mask(op):
+            self._bwd.append(self._call("rn_stem_clip_wgrad", L.C.byref(op.dfull), self._p(op.x8), self._p(dy),
+                                        self._gp(op.weight), self._p(op.clip_ext), *self._wgrad_ws_args(), sp))
+        else:
+            self._bwd.append(self._wgrad_call(op.dfull, self._p(op.x8), self._p(dy), self._gp(op.weight)))
+        self.param_done_at[op.weight] = len(self._bwd)
+        if op.bn:
+            self._bwd.append(self._call("rn_stem_shift_grad", L.C.byref(op.dfull), self._p(dy),
+                                        op.wsrc, self._gp(op.bn["beta"]), self._p(self.stem_ws), sp))
+            if op.quant and self._stem_clip_mask(op):
+                self._bwd.append(self._call("rn_stem_clip_dbeta", L.C.byref(op.dfull), self._p(op.clip_ext),
+                                            op.wsrc, self._gp(op.bn["beta"]), sp))
+            elif op.quant:
+                _, _, sc, sh = op.bn_ptrs
+                self._bwd.append(self._call("rn_stem_quant_clip_grad", L.C.byref(op.dfull), self._in_ptr, sc, sh,
+                                            self._ap(op.quant["minmax"]),
+                                            self._p(dy), op.wsrc, self._gp(op.bn["beta"]), sp))
+            self.param_done_at[op.bn["beta"]] = len(self._bwd)
+            self.param_done_at[op.bn["gamma"]] = len(self._bwd)
+
+    def _bn_bwd_part_call(self, op, part, nblocks, dy, out, add):
+        """rn_bn_bwd_part: finalize + apply over a reduction another kernel left in `part`."""
+        return self._call("rn_bn_bwd_part", L.C.byref(op.desc), self._p(part), nblocks, self._p(self.act(op.x)),
+                          self._p(dy), self._p(out), self._p(add), self._pp(op.gamma), op.sm, op.si, op.sc, op.sh,
+                          self._gp(op.gamma), self._gp(op.beta), self._wsp, self._spv)
+
+    def _bwd_bn(self, op, dy, gs):
+        x, sp = op.x, self._spv
+        out, add = (gs.contribute(x) if x.needs_grad else (None, None))
+        w = self._gw.get(id(op.y))
+        # (may the kernel that completed dy, a conv dgrad or a pooling backward, carry this BN's reduction?)
+        fusable = bool(self._bwd_fusion and not op.desc.dy2 and w and w[0] in ("dgrad", "pool") and dy is w[4])
+        if op.use_global_stats:
+            # moving statistics are constants of the graph (fix_bn): dx = gamma*invstd*dz
+            self._bwd.append(self._call("rn_bn_bwd_global", L.C.byref(op.desc), self._p(self.act(x)), self._p(dy),
+                                        self._p(out), self._p(add), self._pp(op.gamma), self._ap(op.mean),
+                                        self._ap(op.var), op.sc, op.sh,
+                                        self._gp(op.gamma), self._gp(op.beta), self._wsp, sp))
+        elif fusable and w[0] == "dgrad" and \
+                op.y.c % 8 == 0 and op.y.c == op.y.cp and \
+                (self._bwd_all or self._big_tile(w[2], 1) or self._grouped_fuse(w[2], 1)) and \
+                not self._depthwise(w[2]) and \
+                (not op.desc.clip or self._big_tile(w[2], 1)):  # (the clip: bf16 LDS-DMA tiles)
+            self._bwd_bn_from_dgrad(op, dy, out, add, w)
+        elif fusable and not op.desc.clip and w[0] == "pool" and \
+                op.y.c == op.y.cp and self.dtype == BF16 and \
+                int(self.lib.rn_pool_bwd_bnred_blocks(L.C.byref(w[2].desc))) > 0:
+            # the max-pool backward that completes this BN's output gradient (the stem's bn0 ->
+            # relu0 -> pool0) also reduces its backward; the BN then needs only finalize + apply
+            _, pi, pop, pdy, pout, padd = w
+            op.bnred_blocks = int(self.lib.rn_pool_bwd_bnred_blocks(L.C.byref(pop.desc)))
+            op.bnred = self._zeros(op.bnred_blocks * op.y.cp * 2, self.torch.float32)
+            self._bwd[pi] = self._call("rn_pool_bwd_bnred", L.C.byref(pop.desc), self._p(pdy), self._p(pop.argmax),
+                                       self._p(pout), self._p(padd), self._p(self.act(x)), op.sm, op.sc, op.sh,
+                                       int(op.relu), self._p(op.bnred), sp)
+            self._bwd.append(self._bn_bwd_part_call(op, op.bnred, op.bnred_blocks, dy, out, add))
+        elif op.pre_part is not None and not op.desc.dy2:
+            # the reduction was done by the residual add's ReLU backward (rn_relu_bwd_bnred)
+            self._bwd.append(self._bn_bwd_part_call(op, op.pre_part, op.pre_nrb, dy, out, add))
+        else:
+            self._bwd.append(self._call("rn_bn_bwd", L.C.byref(op.desc), self._p(self.act(x)), self._p(dy),
+                                        self._p(out), self._p(add), self._pp(op.gamma), op.sm, op.si, op.sc,
+                                        op.sh, self._gp(op.gamma), self._gp(op.beta), self._wsp, sp))
+        self.param_done_at[op.gamma] = len(self._bwd)
+        self.param_done_at[op.beta] = len(self._bwd)
+
+    def _bwd_bn_from_dgrad(self, op, dy, out, add, w):
+        """The conv dgrad that completes this BN's output gradient also reduces its backward
+        (sum dz, sum dz*(x - mean)); the BN then needs only finalize + apply. `w`: that dgrad's writer record."""
+        x, sp = op.x, self._spv
+        _, ci, cop, cdy, cout, cadd = w
+        op.bnred_blocks = int(self.lib.rn_conv_bnred_blocks(L.C.byref(cop.desc)))
+        op.bnred = self._zeros(op.bnred_blocks * op.y.cp * 2, self.torch.float32)
+        if self._bn_recompute_ok(op, cop, cadd, self._recompute_min_bytes):
+            # pass 1 only reduces (the BN-width gradient is never written), finalize, then the same
+            # dgrad recomputed with the BN backward applied in its epilogue (bit-identical)
+            op.coef = self._zeros(4 * op.y.cp, self.torch.float32)
+            self._bwd[ci] = self._call("rn_conv_bwd_data_bnred", L.C.byref(cop.desc), self._p(cdy), self._p(cop.wc),
+                                       None, None, self._p(self.act(x)), op.sm, op.sc,
+                                       op.sh, int(op.relu), self._p(op.bnred), sp)
+            self._bwd.append(self._call("rn_bn_bwd_finalize", L.C.byref(op.desc), self._p(op.bnred), op.bnred_blocks,
+                                        self._pp(op.gamma), op.sm, op.si,
+                                        self._gp(op.gamma), self._gp(op.beta), self._p(op.coef), sp))
+            self._bwd.append(self._call("rn_conv_bwd_data_bnapply", L.C.byref(cop.desc), self._p(cdy), self._p(cop.wc),
+                                        self._p(out), self._p(add), self._p(self.act(x)),
+                                        self._p(op.coef), op.sc, op.sh, int(op.relu), sp))
+            # the gradient of the BN's output is never stored: the buffer bound for it when conv1's data
+            # gradient was planned is released here (this dgrad was its only writer, the BN its only
+            # reader; no bound call holds its pointer any more) -- every reference: the buffer table and
+            # the writer record here, the binders' own names as they return (nothing is allocated in between)
+            assert self._grads.get(id(cop.x)) is cout
+            del self._grads[id(cop.x)]
+            self._gw[id(op.y)] = ("other",)
+            op.recomputed = True
+            return
+        if op.desc.clip:  # (a folded quantizer straight-through clip)
+            self._bwd[ci] = self._call("rn_conv_bwd_data_bnred_clip", L.C.byref(cop.desc), self._p(cdy),
+                                       self._p(cop.wc), self._p(cout), self._p(cadd), self._p(self.act(x)), op.sm,
+                                       op.sc, op.sh, int(op.relu), L.C.c_void_p(op.desc.clip), self._p(op.bnred), sp)
+        else:
+            self._bwd[ci] = self._call("rn_conv_bwd_data_bnred", L.C.byref(cop.desc), self._p(cdy), self._p(cop.wc),
+                                       self._p(cout), self._p(cadd), self._p(self.act(x)), op.sm, op.sc, op.sh,
+                                       int(op.relu), self._p(op.bnred), sp)
+        self._bwd.append(self._bn_bwd_part_call(op, op.bnred, op.bnred_blocks, dy, out, add))
+
+    def _bwd_affine(self, op, dy, gs):
+        """The global-statistics BN backward with mean 0, variance 1, eps 0: dz = dy*[y > 0],
+        dscale = sum(dz*x), dbias = sum(dz), dx = scale*dz."""
+        x = op.x
+        out, add = (gs.contribute(x) if x.needs_grad else (None, None))
+        if op.gamma is None or op.beta is None:
+            op.gscratch = self._zeros(x.cp, self.torch.float32)
+        dg = self._gp(op.gamma) if op.gamma is not None else self._p(op.gscratch)
+        db = self._gp(op.beta) if op.beta is not None else self._p(op.gscratch)
+        self._bwd.append(self._call("rn_bn_bwd_global", L.C.byref(op.desc), self._p(self.act(x)), self._p(dy),
+                                    self._p(out), self._p(add), op.sc, op.zero, op.one,
+                                    op.sc, op.sh, dg, db, self._wsp, self._spv))
+        for nm in (op.gamma, op.beta):
+            if nm is not None:
+                self.param_done_at[nm] = len(self._bwd)
+
+    def _bwd_quant(self, op, dy, gs):
+        if op.x.needs_grad and id(op) in self._folds:
+            # straight-through: the gradient passes unchanged to the BN output, whose backward
+            # applies the clip; the conv that wrote dy stays its last writer (BN reduction fusion)
+            gs.alias(op.x, dy)
+            bn = self._folds[id(op)]
+            bn.qorder.append(op)
+            if bn.qpair:
+                self._gw[id(op.x)] = ("other",)
+            elif id(op.y) in self._gw:
+                self._gw[id(op.x)] = self._gw[id(op.y)]
+        elif op.x.needs_grad:
+            out, add = gs.contribute(op.x)
+            self._bwd.append(self._call("rn_quant_int8_bwd", self.dtype, op.x.numel, self._p(self.act(op.x)),
+                                        self._p(dy), self._p(out), self._ap(op.q["minmax"]), 0, self._p(add),
+                                        self._spv))
+
+    def _bwd_pact(self, op, dy, gs):
+        """dx = dy * [x < gamma] and dgamma = sum dy * [x >= gamma] in one pass (+ the ordered sum of its
+        block partials, which writes the gradient). This call is the last writer of x's gradient and
+        fuses no BatchNorm reduction: the BatchNorm that produced x runs its own rn_bn_bwd."""
+        if self._pact_ws is None:  # (one buffer, made by the first op that needs it)
+            nmax = max(o.x.numel for o in self.plan.ops if o.kind == "pact")
+            self._pact_ws = self._zeros(int(self.lib.rn_pact_bwd_ws_bytes(nmax)) // 4, self.torch.float32)
+        if op.x.needs_grad:
+            out, add = gs.contribute(op.x)
+            self._gw[id(op.x)] = ("other",)
+        else:  # (no consumer of dx: a scratch buffer takes it)
+            out, add = self._zeros(op.x.numel, self.tdtype), None
+            self._grads[("pact_dx", id(op))] = out
+        self._bwd.append(self._call("rn_pact_bwd", self.dtype, op.x.numel, self._p(self.act(op.x)), self._p(dy),
+                                    self._pp(op.gamma), self._p(out), self._p(add),
+                                    self._gp(op.gamma), self._p(self._pact_ws), self._spv))
+        self.param_done_at[op.gamma] = len(self._bwd)
+
+    def _bwd_gdrq(self, op, dy, gs):
+        """dx = dy * [|x| <= alpha], the boundary included (rn_gdrq_bwd; the BatchNorm-folded clip and
+        rn_quant_int8_bwd exclude it), with the alpha the forward left. alpha has no gradient. As for
+        PACT this call is the last writer of x's gradient and fuses no BatchNorm reduction."""
+        if op.x.needs_grad:
+            out, add = gs.contribute(op.x)
+            self._gw[id(op.x)] = ("other",)
+            self._bwd.append(self._call("rn_gdrq_bwd", self.dtype, op.x.numel, self._p(self.act(op.x)),
+                                        self._p(dy), self._ap(op.alpha), self._p(out), self._p(add), self._spv))
+
+    def _bwd_relu(self, op, dy, gs):
+        if op.x.needs_grad:
+            out, add = gs.contribute(op.x)
+            self._bwd.append(self._call("rn_relu_bwd", op.y.numel, self.dtype, self._p(self.act(op.y)),
+                                        self._p(dy), self._p(out), self._p(add), self._spv))
+
+    def _bwd_add(self, op, dy, gs):
+        g = dy
+        if op.relu:
+            # held by the executor: the bound call keeps only the raw pointer (a dropped
+            # tensor would be recycled by the caching allocator while the plan writes it)
+            gbuf = self._zeros(op.y.numel, self.tdtype)
+            self._grads[("relu_add", id(op))] = gbuf
+            # the BatchNorms applied inside this add (rn_bn_apply_add) get their backward
+            # reductions from the same pass (rn_relu_bwd_bnred)
+            inside = [b for b in (op.bn_a, op.bn_b) if b is not None]
+            bns = [b for b in inside if not b.use_global_stats]
+            # (round 4's opt-in RN_RELU_BNRED_DGRAD -- this pass in the next unit's conv1 data-gradient
+            # epilogue -- measured 3 % slower on C4 and was removed in round 5: the epilogue streamed
+            # its extra tensors at ~3.5 TB/s, this pass runs at ~5.5)
+            if bns and len(bns) == len(inside):
+                for b in bns:
+                    b.pre_nrb = int(self.lib.rn_bn_reduce_blocks(L.C.byref(b.desc)))
+                    b.pre_part = self._zeros(b.pre_nrb * b.x.cp * 2, self.torch.float32)
+                b2 = bns[1] if len(bns) == 2 else None
+                self._bwd.append(self._call("rn_relu_bwd_bnred", L.C.byref(bns[0].desc), self._p(self.act(op.y)),
+                    self._p(dy), self._p(gbuf), self._p(self.act(bns[0].x)), bns[0].sm, self._p(bns[0].pre_part),
+                    self._p(self.act(b2.x)) if b2 else None, b2.sm if b2 else None,
+                    self._p(b2.pre_part) if b2 else None, self._spv))
             else:
-                dy = gs.read(op.y) if op.kind != "softmax" else None
-            if dy is None:
-                continue
-            if op.kind == "fc":
-                x = op.x
-                self._bwd.append(self._wgrad_call(op.desc, self._p(self.act(x)), self._p(dy), self._gp(op.weight), sp))
-                if op.bias:
-                    self._bwd.append(self._call("rn_col_sum", self.dtype, x.n, op.nh, _pad8(op.nh), self._p(dy),
-                                                self._gp(op.bias), 0, sp))
-                    self.param_done_at[op.bias] = len(self._bwd)
-                self.param_done_at[op.weight] = len(self._bwd)
-                if x.needs_grad:
-                    out, add = gs.contribute(x)
-                    self._bwd.append(self._call("rn_conv_bwd_data", L.C.byref(op.desc), self._p(dy), self._p(op.wc),
-                                                self._p(out), self._p(add), sp))
-            elif op.kind == "conv":
-                x = op.x
-                if op.xf is not None:  # input = BN+ReLU(bn input), applied on load
-                    ws = self.wgrad_ws is not None and int(self.lib.rn_conv_wgrad_ws_bytes(L.C.byref(op.desc))) > 0
-                    self._bwd.append(self._call("rn_conv_bwd_filter_x", L.C.byref(op.desc), self._p(self.act(op.xf.x)),
-                                                self._p(dy), self._gp(op.weight), op.xf.sc, op.xf.sh,
-                                                self._p(self.wgrad_ws) if ws else None,
-                                                self.wgrad_ws_bytes if ws else 0, sp))
-                elif getattr(op, "qsrc", None) is not None and op.qsrc.codes_wgrad:  # the input's codes, x its unit
-                    q, ws = op.qsrc, self.wgrad_ws is not None
-                    self._bwd.append(self._call("rn_conv_bwd_filter_i8", L.C.byref(op.desc), self._p(q.codes),
-                                                self._p(q.unit), self._p(dy), self._gp(op.weight),
-                                                self._p(self.wgrad_ws) if ws else None,
-                                                self.wgrad_ws_bytes if ws else 0, sp))
-                else:
-                    self._bwd.append(self._wgrad_call(op.desc, self._p(self.act(x)), self._p(dy), self._gp(op.weight),
-                                                      sp))
-                self.param_done_at[op.weight] = len(self._bwd)
-                if x.needs_grad:
-                    out, add = gs.contribute(x)
-                    self._bwd.append(self._call("rn_conv_bwd_data", L.C.byref(op.desc), self._p(dy), self._p(op.wc),
-                                                self._p(out), self._p(add), sp))
-                    self._gw[id(x)] = ("dgrad", len(self._bwd) - 1, op, dy, out, add)
-                if op.res is not None and op.res.needs_grad:
-                    gs.alias(op.res, dy)
-            elif op.kind == "stem":
-                nch = self._stem_chunks(op, dy)
-                if nch > 1:
-                    # the stem BN's dx (= dy here) per image chunk, each chunk's weight gradient (side
-                    # stream) starting as soon as its rows are applied: only the last chunk's wgrad
-                    # stays on the step's critical path (rn_bn_bwd then reduces + finalizes only)
-                    bname, bfn, bargs = self._bwd[-1]
-                    if bname == "rn_bn_bwd":
-                        self._bwd[-1] = (bname, bfn, bargs[:3] + (None,) + bargs[4:])
-                    else:  # rn_bn_bwd_part: finalize only, its coefficients where rn_bn_bwd_apply_rows reads
-                        # them (after the reduction partials of rn_bn_bwd's own layout in the workspace)
-                        bd, part, nrb, xp_, dyp_, dxp_, _, gp_, smp, sip, scp, shp, dgp, dbp, wsp_, _ = bargs
-                        coef = wsp_.value + 4 * 2 * int(self.lib.rn_bn_reduce_blocks(bd)) * bd._obj.c
-                        self._bwd[-1] = self._call("rn_bn_bwd_finalize", bd, part, nrb, gp_, smp, sip, dgp, dbp,
-                                                   L.C.c_void_p((coef + 15) // 16 * 16), sp)
-                        bargs = (bd, xp_, dyp_, dxp_, None, gp_, smp, sip, scp, shp, dgp, dbp, wsp_, sp)
-                    d = op.dfull
-                    nc = d.n // nch
-                    rows = nc * d.p * d.q
-                    for i in range(nch):
-                        dc = self._conv_desc(nc, d.h, d.w, d.c, d.c_real, d.k, (d.r, d.s), (d.stride_h, d.stride_w),
-                                             (d.pad_h, d.pad_w))
-                        self._descs.append(dc)
-                        self._bwd.append(self._call("rn_bn_bwd_apply_rows", bargs[0], bargs[1], bargs[2], bargs[3],
-                                                    None, bargs[8], bargs[9], bargs[12], i * rows, rows, sp))
-                        dyc = L.C.c_void_p(self._p(dy).value + i * rows * d.k_pad * 2)
-                        if op.p4:
-                            hp, wp = op.p4
-                            self._bwd.append(self._call(
-                                "rn_stem_conv_wgrad_p4", L.C.byref(dc),
-                                L.C.c_void_p(op.x8.data_ptr() + i * nc * hp * wp * 4 * 2), dyc, self._gp(op.weight),
-                                hp, wp, sp))
-                        else:  # the int8 stem: NHWC-8 chunks, clip masks in channels c_real..
-                            ws = self.wgrad_ws is not None
-                            self._bwd.append(self._call(
-                                "rn_stem_clip_wgrad_chunk", L.C.byref(dc),
-                                L.C.c_void_p(op.x8.data_ptr() + i * nc * d.h * d.w * 8 * 2), dyc, self._gp(op.weight),
-                                self._p(op.clip_ext), self._p(self.wgrad_ws) if ws else None,
-                                self.wgrad_ws_bytes if ws else 0, int(i == 0), int(i == nch - 1), sp))
-                elif op.p4:
-                    self._bwd.append(self._call("rn_stem_conv_wgrad_p4", L.C.byref(op.dfull), self._p(op.x8),
-                                                self._p(dy), self._gp(op.weight), op.p4[0], op.p4[1], sp))
-                elif self._stem_clip_mask(op):
-                    ws = self.wgrad_ws is not None
-                    self._bwd.append(self._call("rn_stem_clip_wgrad", L.C.byref(op.dfull), self._p(op.x8),
-                                                self._p(dy), self._gp(op.weight), self._p(op.clip_ext),
-                                                self._p(self.wgrad_ws) if ws else None,
-                                                self.wgrad_ws_bytes if ws else 0, sp))
-                else:
-                    self._bwd.append(self._wgrad_call(op.dfull, self._p(op.x8), self._p(dy), self._gp(op.weight), sp))
-                self.param_done_at[op.weight] = len(self._bwd)
-                if op.bn:
-                    self._bwd.append(self._call("rn_stem_shift_grad", L.C.byref(op.dfull), self._p(dy),
-                                                op.wsrc, self._gp(op.bn["beta"]), self._p(self.stem_ws), sp))
-                    if op.quant and self._stem_clip_mask(op):
-                        self._bwd.append(self._call("rn_stem_clip_dbeta", L.C.byref(op.dfull), self._p(op.clip_ext),
-                                                    op.wsrc, self._gp(op.bn["beta"]), sp))
-                    elif op.quant:
-                        _, _, sc, sh = op.bn_ptrs
-                        self._bwd.append(self._call("rn_stem_quant_clip_grad", L.C.byref(op.dfull),
-                                                    self._in_ptr, sc, sh, self._ap(op.quant["minmax"]),
-                                                    self._p(dy), op.wsrc, self._gp(op.bn["beta"]), sp))
-                    self.param_done_at[op.bn["beta"]] = len(self._bwd)
-                    self.param_done_at[op.bn["gamma"]] = len(self._bwd)
-            elif op.kind == "bn":
-                x = op.x
-                out, add = (gs.contribute(x) if x.needs_grad else (None, None))
-                w = self._gw.get(id(op.y))
-                if op.use_global_stats:
-                    # moving statistics are constants of the graph (fix_bn): dx = gamma*invstd*dz
-                    self._bwd.append(self._call("rn_bn_bwd_global", L.C.byref(op.desc), self._p(self.act(x)),
-                                                self._p(dy), self._p(out), self._p(add), self._pp(op.gamma),
-                                                self._ap(op.mean), self._ap(op.var), op.sc, op.sh,
-                                                self._gp(op.gamma), self._gp(op.beta), wsp, sp))
-                elif bwd_fusion and not op.desc.dy2 and w and w[0] == "dgrad" and dy is w[4] and \
-                        op.y.c % 8 == 0 and op.y.c == op.y.cp and \
-                        (bwd_all or self._big_tile(w[2], 1) or self._grouped_fuse(w[2], 1)) and \
-                        not self._depthwise(w[2]) and \
-                        (not op.desc.clip or self._big_tile(w[2], 1)):  # (the clip: bf16 LDS-DMA tiles)
-                    # the conv dgrad that completes this BN's output gradient also reduces its backward
-                    # (sum dz, sum dz*(x - mean)); the BN then needs only finalize + apply
-                    _, ci, cop, cdy, cout, cadd = w
-                    op.bnred_blocks = int(self.lib.rn_conv_bnred_blocks(L.C.byref(cop.desc)))
-                    op.bnred = self._zeros(op.bnred_blocks * op.y.cp * 2, self.torch.float32)
-                    if self._bn_recompute_ok(op, cop, cadd, recompute_min_bytes):
-                        # pass 1 only reduces (the BN-width gradient is never written), finalize, then the same
-                        # dgrad recomputed with the BN backward applied in its epilogue (bit-identical)
-                        op.coef = self._zeros(4 * op.y.cp, self.torch.float32)
-                        self._bwd[ci] = self._call("rn_conv_bwd_data_bnred", L.C.byref(cop.desc), self._p(cdy),
-                                                   self._p(cop.wc), None, None, self._p(self.act(x)), op.sm, op.sc,
-                                                   op.sh, int(op.relu), self._p(op.bnred), sp)
-                        self._bwd.append(self._call("rn_bn_bwd_finalize", L.C.byref(op.desc), self._p(op.bnred),
-                                                    op.bnred_blocks, self._pp(op.gamma), op.sm, op.si,
-                                                    self._gp(op.gamma), self._gp(op.beta), self._p(op.coef), sp))
-                        self._bwd.append(self._call("rn_conv_bwd_data_bnapply", L.C.byref(cop.desc), self._p(cdy),
-                                                    self._p(cop.wc), self._p(out), self._p(add), self._p(self.act(x)),
-                                                    self._p(op.coef), op.sc, op.sh, int(op.relu), sp))
-                        # the gradient of the BN's output is never stored: the buffer bound for it when conv1's data
-                        # gradient was planned is released here (this dgrad was its only writer, the BN its only
-                        # reader; no bound call holds its pointer any more) -- every reference: the buffer table,
-                        # the writer record and this loop's own names
-                        assert self._grads.get(id(cop.x)) is cout
-                        del self._grads[id(cop.x)]
-                        self._gw[id(op.y)] = ("other",)
-                        w = dy = cout = None
-                        op.recomputed = True
-                    elif op.desc.clip:  # (a folded quantizer straight-through clip)
-                        self._bwd[ci] = self._call("rn_conv_bwd_data_bnred_clip", L.C.byref(cop.desc),
-                                                   self._p(cdy), self._p(cop.wc), self._p(cout), self._p(cadd),
-                                                   self._p(self.act(x)), op.sm, op.sc, op.sh, int(op.relu),
-                                                   L.C.c_void_p(op.desc.clip), self._p(op.bnred), sp)
-                    else:
-                        self._bwd[ci] = self._call("rn_conv_bwd_data_bnred", L.C.byref(cop.desc), self._p(cdy),
-                                                   self._p(cop.wc), self._p(cout), self._p(cadd),
-                                                   self._p(self.act(x)), op.sm, op.sc, op.sh, int(op.relu),
-                                                   self._p(op.bnred), sp)
-                    if not op.recomputed:
-                        self._bwd.append(self._call("rn_bn_bwd_part", L.C.byref(op.desc), self._p(op.bnred),
-                                                    op.bnred_blocks, self._p(self.act(x)), self._p(dy), self._p(out),
-                                                    self._p(add), self._pp(op.gamma), op.sm, op.si, op.sc, op.sh,
-                                                    self._gp(op.gamma), self._gp(op.beta), wsp, sp))
-                elif bwd_fusion and not op.desc.dy2 and not op.desc.clip and w and w[0] == "pool" and dy is w[4] and \
-                        op.y.c == op.y.cp and self.dtype == BF16 and os.environ.get("RN_POOL_BN_FUSION", "1") == "1" and \
-                        int(self.lib.rn_pool_bwd_bnred_blocks(L.C.byref(w[2].desc))) > 0:
-                    # the max-pool backward that completes this BN's output gradient (the stem's bn0 ->
-                    # relu0 -> pool0) also reduces its backward; the BN then needs only finalize + apply
-                    _, pi, pop, pdy, pout, padd = w
-                    op.bnred_blocks = int(self.lib.rn_pool_bwd_bnred_blocks(L.C.byref(pop.desc)))
-                    op.bnred = self._zeros(op.bnred_blocks * op.y.cp * 2, self.torch.float32)
-                    self._bwd[pi] = self._call("rn_pool_bwd_bnred", L.C.byref(pop.desc), self._p(pdy),
-                                               self._p(pop.argmax), self._p(pout), self._p(padd),
-                                               self._p(self.act(x)), op.sm, op.sc, op.sh, int(op.relu),
-                                               self._p(op.bnred), sp)
-                    self._bwd.append(self._call("rn_bn_bwd_part", L.C.byref(op.desc), self._p(op.bnred),
-                                                op.bnred_blocks, self._p(self.act(x)), self._p(dy), self._p(out),
-                                                self._p(add), self._pp(op.gamma), op.sm, op.si, op.sc, op.sh,
-                                                self._gp(op.gamma), self._gp(op.beta), wsp, sp))
-                elif getattr(op, "pre_part", None) is not None and not op.desc.dy2:
-                    # the reduction was done by the residual add's ReLU backward (rn_relu_bwd_bnred)
-                    self._bwd.append(self._call("rn_bn_bwd_part", L.C.byref(op.desc), self._p(op.pre_part),
-                                                op.pre_nrb, self._p(self.act(x)), self._p(dy), self._p(out),
-                                                self._p(add), self._pp(op.gamma), op.sm, op.si, op.sc, op.sh,
-                                                self._gp(op.gamma), self._gp(op.beta), wsp, sp))
-                else:
-                    self._bwd.append(self._call("rn_bn_bwd", L.C.byref(op.desc), self._p(self.act(x)), self._p(dy),
-                                                self._p(out), self._p(add), self._pp(op.gamma), op.sm, op.si, op.sc,
-                                                op.sh, self._gp(op.gamma), self._gp(op.beta), wsp, sp))
-                self.param_done_at[op.gamma] = len(self._bwd)
-                self.param_done_at[op.beta] = len(self._bwd)
-            elif op.kind == "affine":
-                # the global-statistics BN backward with mean 0, variance 1, eps 0: dz = dy*[y > 0],
-                # dscale = sum(dz*x), dbias = sum(dz), dx = scale*dz
-                x = op.x
-                out, add = (gs.contribute(x) if x.needs_grad else (None, None))
-                if op.gamma is None or op.beta is None:
-                    op.gscratch = self._zeros(x.cp, self.torch.float32)
-                dg = self._gp(op.gamma) if op.gamma is not None else self._p(op.gscratch)
-                db = self._gp(op.beta) if op.beta is not None else self._p(op.gscratch)
-                self._bwd.append(self._call("rn_bn_bwd_global", L.C.byref(op.desc), self._p(self.act(x)),
-                                            self._p(dy), self._p(out), self._p(add), op.sc, op.zero, op.one,
-                                            op.sc, op.sh, dg, db, wsp, sp))
-                for nm in (op.gamma, op.beta):
-                    if nm is not None:
-                        self.param_done_at[nm] = len(self._bwd)
-            elif op.kind == "quant":
-                if op.x.needs_grad and id(op) in folds:
-                    # straight-through: the gradient passes unchanged to the BN output, whose backward
-                    # applies the clip; the conv that wrote dy stays its last writer (BN reduction fusion)
-                    gs.alias(op.x, dy)
-                    bn = folds[id(op)]
-                    bn.qorder.append(op)
-                    if bn.qpair:
-                        self._gw[id(op.x)] = ("other",)
-                    elif id(op.y) in self._gw:
-                        self._gw[id(op.x)] = self._gw[id(op.y)]
-                elif op.x.needs_grad:
-                    out, add = gs.contribute(op.x)
-                    self._bwd.append(self._call("rn_quant_int8_bwd", self.dtype, op.x.numel, self._p(self.act(op.x)),
-                                                self._p(dy), self._p(out), self._ap(op.q["minmax"]), 0, self._p(add),
-                                                sp))
-            elif op.kind == "pact":
-                # dx = dy * [x < gamma] and dgamma = sum dy * [x >= gamma] in one pass (+ the ordered sum of its
-                # block partials, which writes the gradient). This call is the last writer of x's gradient and
-                # fuses no BatchNorm reduction: the BatchNorm that produced x runs its own rn_bn_bwd
-                if self._pact_ws is None:
-                    nmax = max(o.x.numel for o in plan.ops if o.kind == "pact")
-                    self._pact_ws = self._zeros(int(self.lib.rn_pact_bwd_ws_bytes(nmax)) // 4, self.torch.float32)
-                if op.x.needs_grad:
-                    out, add = gs.contribute(op.x)
-                    self._gw[id(op.x)] = ("other",)
-                else:  # (no consumer of dx: a scratch buffer takes it)
-                    out, add = self._zeros(op.x.numel, self.tdtype), None
-                    self._grads[("pact_dx", id(op))] = out
-                self._bwd.append(self._call("rn_pact_bwd", self.dtype, op.x.numel, self._p(self.act(op.x)),
-                                            self._p(dy), self._pp(op.gamma), self._p(out), self._p(add),
-                                            self._gp(op.gamma), self._p(self._pact_ws), sp))
-                self.param_done_at[op.gamma] = len(self._bwd)
-            elif op.kind == "gdrq":
-                # dx = dy * [|x| <= alpha], the boundary included (rn_gdrq_bwd; the BatchNorm-folded clip and
-                # rn_quant_int8_bwd exclude it), with the alpha the forward left. alpha has no gradient. As for
-                # PACT this call is the last writer of x's gradient and fuses no BatchNorm reduction
-                if op.x.needs_grad:
-                    out, add = gs.contribute(op.x)
-                    self._gw[id(op.x)] = ("other",)
-                    self._bwd.append(self._call("rn_gdrq_bwd", self.dtype, op.x.numel, self._p(self.act(op.x)),
-                                                self._p(dy), self._ap(op.alpha), self._p(out), self._p(add), sp))
-            elif op.kind == "relu":
-                if op.x.needs_grad:
-                    out, add = gs.contribute(op.x)
-                    self._bwd.append(self._call("rn_relu_bwd", op.y.numel, self.dtype, self._p(self.act(op.y)),
-                                                self._p(dy), self._p(out), self._p(add), sp))
-            elif op.kind == "add":
-                g = dy
-                if op.relu:
-                    # held by the executor: the bound call keeps only the raw pointer (a dropped
-                    # tensor would be recycled by the caching allocator while the plan writes it)
-                    gbuf = self._zeros(op.y.numel, self.tdtype)
-                    self._grads[("relu_add", id(op))] = gbuf
-                    # the BatchNorms applied inside this add (rn_bn_apply_add) get their backward
-                    # reductions from the same pass (rn_relu_bwd_bnred)
-                    bns = [b for b in (getattr(op, "bn_a", None), getattr(op, "bn_b", None))
-                           if b is not None and not b.use_global_stats and dy is not None]
-                    # (round 4's opt-in RN_RELU_BNRED_DGRAD -- this pass in the next unit's conv1 data-gradient
-                    # epilogue -- measured 3 % slower on C4 and was removed in round 5: the epilogue streamed
-                    # its extra tensors at ~3.5 TB/s, this pass runs at ~5.5)
-                    if bns and len(bns) == len([b for b in (op.bn_a, op.bn_b) if b is not None]):
-                        for b in bns:
-                            b.pre_nrb = int(self.lib.rn_bn_reduce_blocks(L.C.byref(b.desc)))
-                            b.pre_part = self._zeros(b.pre_nrb * b.x.cp * 2, self.torch.float32)
-                        b2 = bns[1] if len(bns) == 2 else None
-                        self._bwd.append(self._call(
-                            "rn_relu_bwd_bnred", L.C.byref(bns[0].desc), self._p(self.act(op.y)), self._p(dy),
-                            self._p(gbuf), self._p(self.act(bns[0].x)), bns[0].sm, self._p(bns[0].pre_part),
-                            self._p(self.act(b2.x)) if b2 else None, b2.sm if b2 else None,
-                            self._p(b2.pre_part) if b2 else None, sp))
-                    else:
-                        self._bwd.append(self._call("rn_relu_bwd", op.y.numel, self.dtype, self._p(self.act(op.y)),
-                                                    self._p(dy), self._p(gbuf), None, sp))
-                    g = gbuf
-                for t in (op.a, op.b):
-                    if t.needs_grad:
-                        gs.alias(t, g)
-            elif op.kind == "pool":
-                x = op.x
-                if x.needs_grad:
-                    out, add = gs.contribute(x)
-                    self._bwd.append(self._call("rn_pool_bwd", L.C.byref(op.desc), self._p(dy), self._p(op.argmax),
-                                                self._p(out), self._p(add), sp))
-                    self._gw[id(x)] = ("pool", len(self._bwd) - 1, op, dy, out, add)
-        self._gw = {}  # (the writer records hold gradient tensors and serve only while the plan is bound)
+                self._bwd.append(self._call("rn_relu_bwd", op.y.numel, self.dtype, self._p(self.act(op.y)),
+                                            self._p(dy), self._p(gbuf), None, self._spv))
+            g = gbuf
+        for t in (op.a, op.b):
+            if t.needs_grad:
+                gs.alias(t, g)
+
+    def _bwd_pool(self, op, dy, gs):
+        x = op.x
+        if x.needs_grad:
+            out, add = gs.contribute(x)
+            self._bwd.append(self._call("rn_pool_bwd", L.C.byref(op.desc), self._p(dy), self._p(op.argmax),
+                                        self._p(out), self._p(add), self._spv))
+            self._gw[id(x)] = ("pool", len(self._bwd) - 1, op, dy, out, add)
 
     # ------------------------------------------------------------------ update
     def _build_update(self):

@@ -32,7 +32,7 @@ def main():
     import torch
     from rn import graphs
     from rn import lib as L
-    from rn.executor import Plan, _pad8
+    from rn.plan import Plan, _pad8
     sym = {"resnet50": graphs.resnet50, "resnext50": graphs.resnext50_32x4d,
            "resnet50_int8": graphs.resnet50_int8, "resnet50_pact": graphs.resnet50_pact,
            "resnet50_gdrq": graphs.resnet50_gdrq,

@@ -29,7 +29,7 @@ def _weight_items(torch, L, dev):
     """Both packs' item arrays over the dense convolution weights of ResNet-50 (batch-independent), sharing every
     buffer: the master, qw, unit, the state, the int8 codes and the data-gradient copy."""
     from rn import graphs
-    from rn.executor import Plan, _pad8
+    from rn.plan import Plan, _pad8
     plan = Plan(graphs.resnet50_gdrq(), [("data", (2, 3, 224, 224))], [("softmax_label", (2,))])
     keep, qi, gi = [], [], []
     for op in plan.ops:

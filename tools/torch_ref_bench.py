@@ -16,7 +16,7 @@ sys.path[:0] = [REPO, os.path.join(REPO, "resnet.mxnet_amd")]
 
 def unique_convs(batch):
     from rn import graphs
-    from rn.executor import Plan
+    from rn.plan import Plan
     plan = Plan(graphs.resnet50(), [("data", (batch, 3, 224, 224))], [("softmax_label", (batch,))])
     shapes = {}
     for op in plan.ops:

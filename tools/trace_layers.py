@@ -9,7 +9,8 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "resnet.mxnet_amd")]
 from rn import graphs  # noqa: E402
-from rn.executor import Executor, Plan  # noqa: E402
+from rn.executor import Executor  # noqa: E402
+from rn.plan import Plan  # noqa: E402
 from bench import conv_call_bytes  # noqa: E402
 
 CONV_CALLS = ("rn_conv_fwd", "rn_conv_fwd_bnstats", "rn_conv_fwd_x", "rn_conv_bwd_data",
@@ -36,7 +37,7 @@ def main():
     names = {}
     for op in plan.ops:
         for attr in ("desc", "dfull", "d1"):
-            if hasattr(op, attr):
+            if getattr(op, attr, None) is not None:  # (desc defaults to None on every op)
                 names[id(getattr(op, attr))] = op.name
     calls = [(n, a) for n, f, a in ex._fwd_train + ex._bwd if n in CONV_CALLS]
     # host submission order (Dispatch_Id) = the plan's call order on both streams; start times are
