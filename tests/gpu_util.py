@@ -19,6 +19,14 @@ def bf16_round(a):
     return t.numpy().astype(np.float64)
 
 
+def bnrelu_operand(x, sc, sh):
+    """What a kernel with the BatchNorm+ReLU applied on load stages: bf16(max(fmaf(x, sc, sh), 0)) -- the fused
+    multiply-add as a float64 multiply-add (a bf16 times an fp32 value is exact there), rounded to float32 and then
+    to bf16. x: NCHW bf16 values, sc / sh: fp32 values per channel; all as float64 arrays."""
+    v = (x * sc[None, :, None, None] + sh[None, :, None, None]).astype(np.float32)
+    return bf16_round(np.maximum(v, np.float32(0)))
+
+
 def pad8(c):
     return (c + 7) // 8 * 8
 
@@ -49,6 +57,28 @@ def conv_desc(dtype, n, c, h, w, k, r, s, stride, pad, c_real=None, groups=1):
                    k=k, k_pad=pad8(k), r=r, s=s, stride_h=stride, stride_w=stride, pad_h=pad, pad_w=pad, groups=groups)
     L.call("rn_conv_desc_init", C.byref(d))
     return d
+
+
+def rounding_excess(got, ref, sabs, nterms, out_dtype):
+    """|got - ref| / allowed per element, for a sum of `nterms` products of bf16 values (exact in fp32) and added
+    operands accumulated in fp32 and stored once: <= 1 everywhere for any summation order.
+
+    ref: the exact (fp64) sums; sabs: the same sums over the terms' magnitudes (the convolution of |x| and |w|,
+    + |add_src| + |bias|); nterms: r s c / groups, + 1 per added operand (an upper bound serves).
+      delta   = (nterms + 2) 2^-24 sabs   -- nterms - 1 fp32 additions in any order, each within 2^-24 of its
+                                             partial sum, whose magnitude sabs bounds (+ second-order slack)
+      allowed = delta + 2^(floor(log2(|ref| + delta)) - 8)    -- half a bf16 ulp at the accumulator's magnitude
+    (- 24 for an fp32 output). NaN in got gives inf."""
+    got, ref, sabs = (np.asarray(a, dtype=np.float64) for a in (got, ref, sabs))
+    delta = (nterms + 2) * 2.0 ** -24 * sabs
+    mag = np.abs(ref) + delta
+    _, e = np.frexp(mag)  # mag = m 2^e, 0.5 <= m < 1: floor(log2 mag) = e - 1
+    half_ulp = np.where(mag > 0, np.ldexp(1.0, e - 1 - (8 if out_dtype == BF16 else 24)), 0.0)
+    allowed = delta + half_ulp
+    err = np.abs(got - ref)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(err == 0, 0.0, err / allowed)  # (an exact zero where nothing is allowed passes)
+    return np.where(np.isnan(ratio), np.inf, ratio)
 
 
 def rel_err(a, b):

@@ -1,7 +1,9 @@
 """The depthwise 3x3 kernels (dwconv_fwd_kernel / dwconv_dgrad_kernel / dwconv_wgrad_kernel: bf16, groups = c = k,
 pad 1, stride 1 or 2) against the numpy oracle on bf16-rounded inputs, and the same descriptors on the
-block-diagonal tiles (rn_set_tuning 28 = 1 at descriptor-init time), both within the grouped kernels' bars of
-tests/test_kernels_gpu.py: 1.5e-2 of max |ref| for y and dx, 5e-3 for dw."""
+block-diagonal tiles (rn_set_tuning 28 = 1 at descriptor-init time): y and dx, without and with an add_src, within
+one rounding per element (gpu_util.rounding_excess <= 1: fp32 accumulation of the nine products and the added
+operand in any order, then half a bf16 ulp) and within 1.5e-2 of max |ref|, the grouped kernels' bar of
+tests/test_kernels_gpu.py; dw within 5e-3 of max |ref|."""
 import ctypes as C
 import functools
 
@@ -11,7 +13,7 @@ import torch
 
 from oracle import ops
 from rn import lib as L
-from gpu_util import BF16, bf16_round, from_nhwc, p, rel_err, stream, to_nhwc
+from gpu_util import BF16, bf16_round, from_nhwc, p, rel_err, rounding_excess, stream, to_nhwc
 
 pytestmark = pytest.mark.gpu
 
@@ -44,9 +46,13 @@ def _data(case):
     xa = bf16_round(rng.standard_normal((n, c, h, w)))
     y_ref = ops.conv2d_fwd(x, wt, (st, st), (1, 1), c)
     dx_ref, dw_ref = ops.conv2d_bwd(x, wt, dy, (st, st), (1, 1), c)
-    for a in (x, wt, dy, ya, xa, y_ref, dx_ref, dw_ref):
+    # the sums of the terms' magnitudes, for the per-element rounding bar
+    y_sabs = ops.conv2d_fwd(np.abs(x), np.abs(wt), (st, st), (1, 1), c)
+    dx_sabs = ops.conv2d_bwd(x, np.abs(wt), np.abs(dy), (st, st), (1, 1), c)[0]
+    for a in (x, wt, dy, ya, xa, y_ref, dx_ref, dw_ref, y_sabs, dx_sabs):
         a.setflags(write=False)
-    return dict(x=x, wt=wt, dy=dy, ya=ya, xa=xa, y=y_ref, dx=dx_ref, dw=dw_ref, P=P, Q=Q)
+    return dict(x=x, wt=wt, dy=dy, ya=ya, xa=xa, y=y_ref, dx=dx_ref, dw=dw_ref, P=P, Q=Q, y_sabs=y_sabs,
+                dx_sabs=dx_sabs)
 
 
 def _desc(case, off):
@@ -105,9 +111,17 @@ def _run(case, off, gpu, cap=0):
     errs = dict(y=rel_err(from_nhwc(y, c), D["y"]), y_add=rel_err(from_nhwc(y2, c), D["y"] + D["ya"]),
                 dx=rel_err(from_nhwc(dx, c), D["dx"]), dx_add=rel_err(from_nhwc(dx2, c), D["dx"] + D["xa"]),
                 dw=rel_err(dws[0].cpu().numpy().reshape(c, 3, 3, 1).transpose(0, 3, 1, 2), D["dw"]))
-    print("depthwise", case, "off" if off else "dw", "cap", cap, {k: "%.2e" % v for k, v in errs.items()})
+    excess = dict(
+        y=rounding_excess(from_nhwc(y, c), D["y"], D["y_sabs"], 9, BF16).max(),
+        y_add=rounding_excess(from_nhwc(y2, c), D["y"] + D["ya"], D["y_sabs"] + np.abs(D["ya"]), 10, BF16).max(),
+        dx=rounding_excess(from_nhwc(dx, c), D["dx"], D["dx_sabs"], 9, BF16).max(),
+        dx_add=rounding_excess(from_nhwc(dx2, c), D["dx"] + D["xa"], D["dx_sabs"] + np.abs(D["xa"]), 10, BF16).max())
+    print("depthwise", case, "off" if off else "dw", "cap", cap, {k: "%.2e" % v for k, v in errs.items()},
+          "rounding excess", {k: "%.3f" % v for k, v in excess.items()})
     for k, v in errs.items():
         assert v < (TOL_DW if k == "dw" else TOL_Y), (k, v)
+    for k, v in excess.items():
+        assert v <= 1.0, (k, v)
     return dws
 
 

@@ -4,7 +4,7 @@
 
 * per kernel, against the tile run first: y bit for bit, the pivot plane exactly, the partials' per-channel totals
   within fp32 summation-order rounding, rn_bn_fwd_train_part on the partials against the oracle's BatchNorm over the
-  stored y, y against the oracle's convolution;
+  stored y, y against the oracle's convolution within one rounding per element (gpu_util.rounding_excess);
 * the same call twice: bit for bit (how missing MFMA wait states showed in the streamed data gradient);
 * rn_conv_fwd_streamed's rule, on the host.
 """
@@ -17,7 +17,7 @@ import torch
 
 from oracle import ops
 from rn import lib as L
-from gpu_util import BF16, F32, bf16_round, conv_desc, from_nhwc, p, rel_err, stream, to_nhwc
+from gpu_util import BF16, F32, bf16_round, bnrelu_operand, conv_desc, from_nhwc, p, rel_err, rounding_excess, stream, to_nhwc
 
 TOL_BF16 = 1.5e-2  # the bf16 bar of the kernel tests
 KEY = 29           # rn_set_tuning: 0 default, 1 the tiles, 2 / 3 every form streamed, at 32 channels per wave / the default width
@@ -45,10 +45,14 @@ def _inputs(case):
 
 @functools.lru_cache(maxsize=None)
 def _oracle(case, xf, add):
-    """fp64 convolution of the (transformed, bf16-rounded) input, + the residual."""
+    """fp64 convolution of the input -- transformed as the kernel stages it, bf16(max(fmaf(x, sc, sh), 0)): the fma
+    rounds to float32 first, which can move a value across a bf16 tie -- + the residual; and the same sum over the
+    terms' magnitudes, for the per-element rounding bar."""
     x, wt, res, sc, sh = _inputs(case)
-    xa = bf16_round(np.maximum(x * sc[None, :, None, None] + sh[None, :, None, None], 0)) if xf else x
-    return ops.conv2d_fwd(xa, wt, (1, 1), (0, 0)) + (res if add else 0)
+    xa = bnrelu_operand(x, sc, sh) if xf else x
+    ref = ops.conv2d_fwd(xa, wt, (1, 1), (0, 0)) + (res if add else 0)
+    sabs = ops.conv2d_fwd(np.abs(xa), np.abs(wt), (1, 1), (0, 0)) + (np.abs(res) if add else 0)
+    return ref, sabs
 
 
 class _Dev:
@@ -101,9 +105,11 @@ def test_fwd1x1_stream(gpu, case, mode):
             streamed.append(dev.run(mode))
     finally:
         L.call("rn_set_tuning", KEY, 0)
-    y_ref = _oracle(case, mode.startswith("xf"), mode.endswith("res"))
+    y_ref, y_sabs = _oracle(case, mode.startswith("xf"), mode.endswith("res"))
     assert not torch.isnan(y0).any()
     assert rel_err(from_nhwc(y0, k), y_ref) < TOL_BF16
+    # one rounding per element (the streamed outputs below are y0's bits)
+    assert rounding_excess(from_nhwc(y0, k), y_ref, y_sabs, c + mode.endswith("res"), BF16).max() <= 1.0
     u = 2.0 ** -24  # fp32 unit round-off
     for y1, p1 in streamed:
         assert not torch.isnan(y1).any()

@@ -3,6 +3,8 @@
 Tolerances (max |err| / max |ref|):
   fp32 path: 2e-5 (exact-fp32 MFMA products, fp32 accumulation order differs from fp64)
   bf16 path: 1.5e-2 (oracle fed the same bf16-rounded inputs; output rounded to bf16 = 2^-8)
+That bar passes a truncated store or a partial sum kept in bf16: test_conv_rounding_gpu.py holds every bf16 forward
+and data-gradient kernel to one rounding per element (gpu_util.rounding_excess) and to exact integer sums.
 """
 import ctypes as C
 
@@ -12,7 +14,7 @@ import torch
 
 from oracle import ops
 from rn import lib as L
-from gpu_util import BF16, F32, bf16_round, conv_desc, from_nhwc, p, pad8, rel_err, stream, tdt, to_nhwc
+from gpu_util import BF16, F32, bf16_round, conv_desc, from_nhwc, p, pad8, rel_err, rounding_excess, stream, tdt, to_nhwc
 
 pytestmark = pytest.mark.gpu
 
@@ -519,7 +521,7 @@ def test_grouped_conv(gpu, dtype, case):
     assert rel_err(dw_h, dw_ref) < (TOL[dtype] if dtype == F32 else 5e-3)
 
 
-@pytest.mark.parametrize("case", [
+GDIRECT_CASES = [
     (2, 128, 9, 9, 128, 3, 1, 1, 32),     # 4 per group (stage 1), fwd + dgrad direct
     (3, 128, 15, 13, 128, 3, 1, 1, 32),   # ragged rows (13 = 3 blocks of 4 pixels + 1)
     (2, 256, 10, 10, 256, 3, 2, 1, 32),   # 8 per group, stride 2: direct forward, block-diagonal dgrad
@@ -529,13 +531,18 @@ def test_grouped_conv(gpu, dtype, case):
     (2, 512, 6, 7, 512, 3, 1, 1, 32),     # 16 per group (stage 3)
     (2, 512, 9, 9, 512, 3, 2, 1, 32),     # 16 per group, stride 2
     (1, 64, 5, 5, 64, 3, 1, 1, 8),        # 8 per group, fewer channels than a wave has lanes
-])
+]
+
+
+@pytest.mark.parametrize("case", GDIRECT_CASES)
 def test_grouped_conv_direct(gpu, case):
     """The direct grouped kernels (rn_set_tuning 15 = 0: v_dot2_f32_bf16 over 16-byte channel chunks,
     compact weight copies; 4 per group, and 8 per group at stride 2 forward) vs the oracle and vs the
     block-diagonal 64-column tiles (15 = 1): forward and data gradient with an add_src (the residual /
-    gradient accumulation operand), both within one bf16 rounding of the fp64 values. (8 per group at
-    stride 1 and 16 per group run the block-diagonal tiles either way.)"""
+    gradient accumulation operand), both within one bf16 rounding of the fp64 values: every element within
+    gpu_util.rounding_excess <= 1 (fp32 accumulation of the 9 c / groups products and the added operand in any
+    order, then half a bf16 ulp). (8 per group at stride 1 and 16 per group run the block-diagonal tiles either
+    way.)"""
     n, c, h, w, k, r, st, pd, g = case
     rng = np.random.default_rng(13)
     x = bf16_round(rng.standard_normal((n, c, h, w)))
@@ -573,9 +580,14 @@ def test_grouped_conv_direct(gpu, case):
         outs[mode] = (from_nhwc(y, k), from_nhwc(dx, c))
     y_ref = ops.conv2d_fwd(x, wt, (st, st), (pd, pd), g) + ya
     dx_ref = ops.conv2d_bwd(x, wt, dy, (st, st), (pd, pd), g)[0] + xa
+    y_sabs = ops.conv2d_fwd(np.abs(x), np.abs(wt), (st, st), (pd, pd), g) + np.abs(ya)
+    dx_sabs = ops.conv2d_bwd(x, np.abs(wt), np.abs(dy), (st, st), (pd, pd), g)[0] + np.abs(xa)
+    nt = 9 * (c // g) + 1
     for mode in (0, 1):
         assert np.abs(outs[mode][0] - y_ref).max() <= 2 ** -7 * np.abs(y_ref).max(), mode
         assert np.abs(outs[mode][1] - dx_ref).max() <= 2 ** -7 * np.abs(dx_ref).max(), mode
+        assert rounding_excess(outs[mode][0], y_ref, y_sabs, nt, BF16).max() <= 1.0, mode
+        assert rounding_excess(outs[mode][1], dx_ref, dx_sabs, nt, BF16).max() <= 1.0, mode
     assert rel_err(outs[0][0], outs[1][0]) < 4e-3 and rel_err(outs[0][1], outs[1][1]) < 4e-3
 
 
