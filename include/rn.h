@@ -88,6 +88,12 @@ int32_t rn_conv_dgrad_streamed(const rn_conv_desc* d);
  * unpadded, k an unpadded multiple of 128, n h w max(k, c) 2 bytes below 2^31, 224-row statistics blocks
  * (rn_set_tuning 29 = 1: never). 0 otherwise (the tiles). rn_conv_bn_part_rows is 224 either way. */
 int32_t rn_conv_fwd_streamed(const rn_conv_desc* d);
+/* 1 where rn_conv_fwd_x of `d` (bf16 output, no bias) by default runs the LDS-stationary streaming forward kernel
+ * (fwd1x1_lds_stream_kernel): bf16, dense 1x1 stride 1 without padding, c = 256 unpadded, k an unpadded multiple
+ * of 256, n h w max(k, c) 2 bytes below 2^31, 224-row statistics blocks, and enough 224-row blocks for the chip
+ * (rn_set_tuning 30 = 1: never, 2: whatever the size). 0 otherwise (the tiles). rn_conv_fwd_streamed stays 0 for
+ * these shapes; rn_conv_bn_part_rows is 224 either way. */
+int32_t rn_conv_fwd_lds_streamed(const rn_conv_desc* d);
 /* Int8 forward of a quantized convolution (resnet_int8 / attach_quantize_node graphs: conv over
  * Quantization_int8(data) and Quantization_int8(weight), symbol/int8_api.py:120-151). x_codes /
  * w_codes are the int8 codes (value = code * unit; NHWC / KRSC, channel stride d->c bytes, a multiple
@@ -770,7 +776,11 @@ const char* rn_last_error(void);
  *      rows with the weights in registers and the transform, residual and statistics per lane); 29 = 2: that
  *      kernel with 32 channels per wave (default 64 where K % 256 == 0), for every eligible shape in every form;
  *      29 = 3: every form at the default width (by default the C = 128 form without transform, residual and
- *      statistics stays on its tile, which measured faster). */
+ *      statistics stays on its tile, which measured faster),
+ * 30 = 1: the 1x1 / stride-1 forward convolutions from C = 256 into K % 256 == 0 channels (stage 3's conv3) on the
+ *      224-row tiles (default 0: fwd1x1_lds_stream_kernel -- the 224-row block of x stationary in LDS, the
+ *      workgroup sweeping the output channels -- where the row blocks fill the chip); 30 = 2: that kernel for
+ *      every eligible shape whatever its size (tests). */
 int rn_set_tuning(int32_t key, int32_t value);
 int32_t rn_version(void);
 /* Build id baked in at compile time: a hash of the sources (csrc/*.hip, csrc/*.h, include/rn.h) and the

@@ -4960,6 +4960,300 @@ int f1_stream_launch(const rn_conv_desc* d, const void* x, const void* w, void* 
   return rn_check_launch("fwd1x1_stream");
 }
 
+// ---- The same forward at Cin = 256 (stage 3's conv3, 14^2 x 256 -> 1024): fwd1x1_stream_kernel cannot take it -- at
+// KS = 8 the weight fragments of 64 channels are 128 registers per wave, and each wave of each of the K / 256 column
+// groups would reload and re-transform the whole x block. Here the block of x is stationary and the workgroup sweeps
+// the output channels: one 256-thread workgroup per 224-row block (one BatchNorm partial block) loads its 224 x 256
+// block of x once, applies XF once, zeroes the rows past a short block AFTER it and writes the block to LDS (112 KB;
+// 16-byte chunk index XORed with the row: the B-operand ds_read_b128 of 16 rows x 4 chunks are conflict-free). It then
+// sweeps Kout in groups of 256 channels, 64 per wave, with fwd1x1_stream_kernel's lane mapping, row permutation, k
+// order and epilogue at NH = 2 (y and the partials are the tile's bit for bit); a group's weight fragments (128
+// registers) come from global memory (the weight is L2-resident); the next group's are fetched during the current
+// group -- those of the first WN k-steps into a second buffer during its first steps, the others in place behind
+// their last use; the residual is fetched PF steps ahead, across the groups. LDS holds one workgroup
+// per CU, so a wave has the whole register file (launch bound: one wave per SIMD). (p.C and p.ncg are not read.)
+template <int XF, int ADD, int STATS, int PF, int WN>
+__global__ __launch_bounds__(256, 1) void fwd1x1_lds_stream_kernel(F1Args p) {
+  constexpr int KS = 8, CH = 8, RI = 8, SL = 16;  // (the epilogue's layout: fwd1x1_stream_kernel at NH = 2)
+  static_assert(PF >= 1 && PF <= 14, "residual prefetch depth");
+  __shared__ uint4 xs[224 * 32];
+  __shared__ float4 stg[4 * 16 * SL];
+  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // (wid: a scalar)
+  const int g = lane >> 4, i = lane & 15;
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
+  const int rb = lid;
+  const int m0 = rb * 224, rows = min(224, p.M - m0);
+  const int ngrp = p.K / 256;  // column groups
+  const int ec = lane % CH, er = lane / CH;
+  float4* const sw = stg + wid * 16 * SL;
+  const uint4 z4 = make_uint4(0, 0, 0, 0);
+  // Buffer descriptors that END WITH THE BLOCK's last row: a row past a short block is out of range by itself
+  // (loads give zeros, stores are dropped), so an access's offset is one per-lane register + a scalar and the 14
+  // steps' offsets cost no vector registers. A group past the last one: the scalar kPast (out of every range; a
+  // lane's own part is < 2^20, so the sum does not wrap).
+  constexpr uint32_t kPast = 0x80000000u;
+  const int mend = m0 + rows;
+  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, (short)0, mend * 256 * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, (short)0, p.K * 256 * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)p.add, (short)0, mend * p.K * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, (short)0, mend * p.K * 2, 0x00020000);
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  auto ld = [&](__amdgpu_buffer_rsrc_t rs, uint32_t off) __attribute__((always_inline)) {
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
+    return make_uint4(v.x, v.y, v.z, v.w);
+  };
+  // first output channel of this wave in group gi
+  auto kwave = [&](int gi) __attribute__((always_inline)) { return (gi * 4 + wid) * 64; };
+  // byte offset of the lane's epilogue chunk of group gi, step st, instruction j (kOob: a row past the block, a
+  // group past the last)
+  const uint32_t elane = ((uint32_t)er * p.K + 8 * ec) * 2u;  // (the lane's part: < 16 K + 128 bytes)
+  auto eoff = [&](int gi, int st, int j) __attribute__((always_inline)) {
+    const uint32_t u = gi < ngrp ? ((uint32_t)(m0 + st * 16 + RI * j) * p.K + kwave(gi)) * 2u : kPast;
+    return elane + u;
+  };
+  const uint32_t wlane = ((uint32_t)(8 * (i >> 2) + (i & 3)) * 256 + 8 * g) * 2u;  // (< 16 KB)
+  // group gi's fragments of k-step ks (rows permuted as fwd1x1_stream_kernel's; zeros past the last group)
+  auto wload = [&](int gi, int ks, v8s (&dst)[2][2]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {  // channel kwave + 32 h + 8 (i >> 2) + 4 b + (i & 3), inputs 32 ks + 8 g ..
+        const uint32_t u = gi < ngrp ? ((uint32_t)(kwave(gi) + 32 * h + 4 * b) * 256 + ks * 32) * 2u : kPast;
+        dst[h][b] = __builtin_bit_cast(v8s, ld(rs_w, wlane + u));
+      }
+  };
+  // ---- stage the block of x: thread t holds chunk t % 32 of rows t / 32 + 8 pass
+  {
+    const int c = tid & 31, r0 = tid >> 5;
+    float ka[8], kb[8];
+    if constexpr (XF) {
+      *reinterpret_cast<float4*>(ka) = *reinterpret_cast<const float4*>(p.in_sc + 8 * c);
+      *reinterpret_cast<float4*>(ka + 4) = *reinterpret_cast<const float4*>(p.in_sc + 8 * c + 4);
+      *reinterpret_cast<float4*>(kb) = *reinterpret_cast<const float4*>(p.in_sh + 8 * c);
+      *reinterpret_cast<float4*>(kb + 4) = *reinterpret_cast<const float4*>(p.in_sh + 8 * c + 4);
+    }
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {  // (two halves: 14 loads of 16 bytes in flight per thread)
+    uint4 xv[14];
+#pragma unroll
+    for (int ps = 0; ps < 14; ++ps) {
+      const int r = r0 + 8 * (14 * hf + ps);
+      xv[ps] = ld(rs_x, ((uint32_t)(m0 + r) * 256 + 8 * c) * 2u);  // (zeros past the block)
+    }
+#pragma unroll
+    for (int ps = 0; ps < 14; ++ps) {
+      const int r = r0 + 8 * (14 * hf + ps);
+      uint4 o = xv[ps];
+      if constexpr (XF) {
+        float f[8];
+        chunk_to_f(o, f, (const bf16_t*)nullptr);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = fmaxf(fmaf(f[e], ka[e], kb[e]), 0.f);
+        o = f_to_chunk(f, (const bf16_t*)nullptr);
+        const bool ok = r < rows;  // (relu(0 sc + sh) is not zero)
+        o = make_uint4(ok ? o.x : 0u, ok ? o.y : 0u, ok ? o.z : 0u, ok ? o.w : 0u);
+      }
+      xs[r * 32 + (c ^ (r & 15))] = o;
+    }
+    }
+  }
+  v8s wf[KS][2][2], wn[WN > 0 ? WN : 1][2][2];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) wload(0, ks, wf[ks]);
+  uint4 a[PF][2];  // the residual of the next PF steps, a[0] the current step's
+#pragma unroll
+  for (int k = 0; k < PF; ++k)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) a[k][j] = ADD ? ld(rs_a, eoff(0, k, j)) : z4;
+  __syncthreads();
+  for (int gi = 0; gi < ngrp; ++gi) {
+    const int k8 = kwave(gi) + 8 * ec;
+    // (STATS) the sums of rows 0 .. 111 and 112 .. 223 apart, as the 4-wave tile's two wave rows keep them
+    float s1[8], s2[8], t1[8], t2[8], piv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s1[e] = s2[e] = t1[e] = t2[e] = piv[e] = 0.f;
+    // A step's MFMAs are issued one step ahead, into the other of two accumulator sets, in one scheduling region
+    // with the epilogue of the step before: one wave runs per SIMD, so nothing else would cover the MFMAs' time
+    // or the epilogue's LDS turn. (Not across groups: a group's first step waits for its fragments anyway.)
+    v4f acc[2][2][2];
+    auto mma = [&](int st, v4f (&ac)[2][2]) __attribute__((always_inline)) {
+      v8s bf[KS];
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) bf[ks] = __builtin_bit_cast(v8s, xs[(st * 16 + i) * 32 + ((ks * 4 + g) ^ i)]);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) ac[h][b] = v4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int b = 0; b < 2; ++b)
+            ac[h][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][h][b], bf[ks], ac[h][b], 0, 0, 0);
+    };
+    mma(0, acc[0]);
+    // 14 steps, fully unrolled and branch-free (fwd1x1_stream_kernel)
+#pragma unroll
+    for (int st = 0; st < 14; ++st) {
+      // the MFMA results' read wait states, explicitly, once per step (dgrad1x1_stream_kernel): step st's MFMAs
+      // were issued in the region before this one
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("s_nop 7\n\ts_nop 7");
+      __builtin_amdgcn_sched_barrier(0);
+      uint4 an[2] = {z4, z4};
+      if constexpr (ADD) {  // the residual PF steps ahead: of this group, or of the next one's first steps
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          an[j] = ld(rs_a, st + PF < 14 ? eoff(gi, st + PF, j) : eoff(gi + 1, st + PF - 14, j));
+      }
+      if (st < WN) wload(gi + 1, st, wn[st]);  // (compile-time) the next group's fragments of the first WN k-steps
+      if (STATS && st == 7)  // (compile-time) row 112: the second half's sums start
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          t1[e] = s1[e]; t2[e] = s2[e];
+          s1[e] = s2[e] = 0.f;
+        }
+      if (st + 1 < 14) mma(st + 1, acc[(st + 1) & 1]);  // (compile-time)
+      if (st == 12)  // (compile-time) the other k-steps' fragments, in place behind their last use
+#pragma unroll
+        for (int ks = WN; ks < KS; ++ks) wload(gi + 1, ks, wf[ks]);
+      const v4f (&ac)[2][2] = acc[st & 1];
+      // row i's channels 32 h + 8 g + 4 b .. + 3 -> slot 2 (4 h + g) + b of LDS row i
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+          sw[i * SL + ((2 * (4 * h + g) + b) ^ (i & (SL - 1)))] =
+              make_float4(ac[h][b][0], ac[h][b][1], ac[h][b][2], ac[h][b][3]);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's staged rows have landed
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int rr = RI * j + er;
+        float v[8];
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+          const float4 t = sw[rr * SL + ((2 * ec + b) ^ (rr & (SL - 1)))];
+          v[4 * b] = t.x; v[4 * b + 1] = t.y; v[4 * b + 2] = t.z; v[4 * b + 3] = t.w;
+        }
+        if (STATS && st == 0 && j == 0) {  // (compile-time) the pivots: row m0's rounded values, held by lanes er = 0
+          float pv[8];
+          chunk_to_f(f_to_chunk(v, (const bf16_t*)nullptr), pv, (const bf16_t*)nullptr);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) piv[e] = __shfl(pv[e], ec, 64);
+        }
+        if constexpr (ADD) {
+          float af[8];
+          chunk_to_f(a[0][j], af, (const bf16_t*)nullptr);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[e] += af[e];
+        }
+        const uint4 out = f_to_chunk(v, (const bf16_t*)nullptr);
+        if constexpr (STATS) {  // on the stored (rounded) values
+          const bool ok = st * 16 + rr < rows;
+          float gv[8];
+          chunk_to_f(out, gv, (const bf16_t*)nullptr);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float dv = ok ? gv[e] - piv[e] : 0.f;
+            s1[e] += dv;
+            s2[e] = fmaf(dv, dv, s2[e]);
+          }
+        }
+        __builtin_amdgcn_raw_buffer_store_b128(u32x4{out.x, out.y, out.z, out.w}, rs_y, eoff(gi, st, j), 0, 0);
+      }
+#pragma unroll
+      for (int k = 0; k + 1 < PF; ++k)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) a[k][j] = a[k + 1][j];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) a[PF - 1][j] = an[j];
+    }
+    if constexpr (STATS) {  // the RI row lanes of each chunk: xor CH, 2 CH, ..; the lanes er = 0 store
+#pragma unroll
+      for (int o = CH; o < 64; o <<= 1)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          s1[e] += __shfl_xor(s1[e], o, 64);
+          s2[e] += __shfl_xor(s2[e], o, 64);
+          t1[e] += __shfl_xor(t1[e], o, 64);
+          t2[e] += __shfl_xor(t2[e], o, 64);
+        }
+      if (er == 0)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          float* dst = p.part + (int64_t)rb * 3 * p.K + k8 + e;
+          dst[0] = t1[e] + s1[e];
+          dst[p.K] = t2[e] + s2[e];
+          dst[2 * p.K] = piv[e];
+        }
+    }
+#pragma unroll
+    for (int ks = 0; ks < WN; ++ks)
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) wf[ks][h][b] = wn[ks][h][b];
+  }
+}
+
+// residual prefetch depth (steps) and double-buffered k-steps of the weight fragments (the rest are loaded in place
+// behind their last use). Depths 3 / 5 / 8 and 4 / 6 k-steps measured within 2 us of each other (libraries built with
+// other values); all 8 k-steps double buffered spill (tools/kernel_resources.py)
+#ifndef RN_F2_PF
+#define RN_F2_PF 5
+#endif
+#ifndef RN_F2_WN
+#define RN_F2_WN 4
+#endif
+constexpr int kF2Pf = RN_F2_PF, kF2Wn = RN_F2_WN;
+
+// fwd1x1_lds_stream_kernel for this forward? rn_set_tuning 30: 0 = the shapes, forms and sizes that measured faster
+// than the 224-row tiles (profiles/fwd_lds_stream), 1 = never, 2 = every eligible shape and form whatever its size
+// (tests). (224-row BN partial blocks, as the tiles' with rn_set_tuning 9 = 0: f1_stream_shape.)
+bool f2_stream_shape(const rn_conv_desc* d) {
+  return g_tune[RN_TUNE_FWD_LDS_STREAM] != 1 && g_tune[RN_TUNE_IGEMM_ROWS] != 1 && g_tune[RN_TUNE_IGEMM_BIG] != 1 &&
+         !g_tune[RN_TUNE_DIAG_IGEMM_L1] && d->dtype == RN_BF16 && d->groups <= 1 &&
+         d->r == 1 && d->s == 1 && d->stride_h == 1 && d->stride_w == 1 && d->pad_h == 0 && d->pad_w == 0 &&
+         d->c == d->c_real && d->c == 256 && d->k == d->k_pad && d->k % 256 == 0 &&
+         // (the buffer descriptors' byte counts are ints; offsets below kPast)
+         (int64_t)d->n * d->h * d->w * std::max(d->k, d->c) * 2 <= INT32_MAX;
+}
+bool f2_stream_ok(const rn_conv_desc* d, int32_t y_dtype, const float* bias, const float* in_scale, const float* part,
+                  const void* add_src) {
+  if (!f2_stream_shape(d) || y_dtype != RN_BF16 || bias) return false;
+  if (g_tune[RN_TUNE_FWD_LDS_STREAM] >= 2) return true;
+  // One workgroup per CU (its block of x takes the LDS) sweeps all of Kout, where the tiles put K / 128 workgroups
+  // on a row block: the row blocks have to fill the chip. Measured cold (profiles/fwd_lds_stream):
+  // every form faster than its tile at 168, 224 and 896 blocks on 256 CUs, none at 112 and 56.
+  return ceil_div((int64_t)d->n * d->h * d->w, 224) * 32 >= (int64_t)chip_cus() * 21;
+}
+int f2_stream_launch(const rn_conv_desc* d, const void* x, const void* w, void* y, const void* add,
+                     const float* in_sc, const float* in_sh, float* part, hipStream_t st) {
+  F1Args a{};
+  a.x = (const bf16_t*)x; a.w = (const bf16_t*)w; a.y = (bf16_t*)y; a.add = (const bf16_t*)add;
+  a.in_sc = in_sc; a.in_sh = in_sh; a.part = part;
+  a.M = d->n * d->h * d->w; a.C = d->c; a.K = d->k; a.ncg = 1;
+  const dim3 grid((unsigned)ceil_div(a.M, 224));
+#define RN_F2S(XV, AV)                                                                                              \
+  if (part) hipLaunchKernelGGL((fwd1x1_lds_stream_kernel<XV, AV, 1, kF2Pf, kF2Wn>), grid, dim3(256), 0, st, a);     \
+  else hipLaunchKernelGGL((fwd1x1_lds_stream_kernel<XV, AV, 0, kF2Pf, kF2Wn>), grid, dim3(256), 0, st, a);
+#define RN_F2A(XV) \
+  if (add) {       \
+    RN_F2S(XV, 1)  \
+  } else {         \
+    RN_F2S(XV, 0)  \
+  }
+  if (in_sc) {
+    RN_F2A(1)
+  } else {
+    RN_F2A(0)
+  }
+#undef RN_F2A
+#undef RN_F2S
+  return rn_check_launch("fwd1x1_lds_stream");
+}
+
 }  // namespace
 
 extern "C" {
@@ -5030,6 +5324,8 @@ int rn_conv_fwd_x(const rn_conv_desc* d, const void* x, const void* w, void* y, 
     return band_launch(d, x, w, y, 0, as_stream(stream), in_scale, in_shift);
   if (f1_stream_ok(d, y_dtype, bias, in_scale, part, add_src))
     return f1_stream_launch(d, x, w, y, add_src, in_scale, in_shift, part, as_stream(stream));
+  if (f2_stream_ok(d, y_dtype, bias, in_scale, part, add_src))
+    return f2_stream_launch(d, x, w, y, add_src, in_scale, in_shift, part, as_stream(stream));
   IgemmArgs a = make_igemm_args(d, 0);
   a.x = x; a.w = w; a.y = y; a.add = add_src; a.bias = bias; a.stats = part;
   a.in_sc = in_scale; a.in_sh = in_shift;
@@ -5109,6 +5405,11 @@ int32_t rn_conv_dgrad_streamed(const rn_conv_desc* d) { return d && d1_stream_ok
 int32_t rn_conv_fwd_streamed(const rn_conv_desc* d) {  // (a fused form: the input transform set)
   static const float xf = 0.f;
   return d && f1_stream_ok(d, RN_BF16, nullptr, &xf, nullptr, nullptr) ? 1 : 0;
+}
+
+int32_t rn_conv_fwd_lds_streamed(const rn_conv_desc* d) {  // (the form the step calls most: transform + residual + statistics)
+  static const float f = 0.f;
+  return d && f2_stream_ok(d, RN_BF16, nullptr, &f, &f, &f) ? 1 : 0;
 }
 
 int32_t rn_conv_bn_part_rows(const rn_conv_desc* d, int32_t mode) {

@@ -63,6 +63,7 @@ SIGNATURES = {
     "rn_conv_tile": (_i32, [_P, _i32]),
     "rn_conv_dgrad_streamed": (_i32, [_P]),
     "rn_conv_fwd_streamed": (_i32, [_P]),
+    "rn_conv_fwd_lds_streamed": (_i32, [_P]),
     "rn_conv_fwd_i8": (_i32, [_P, _P, _P, _P, _i32, _P, _P, _P, _P, _P]),
     "rn_conv_fwd_i8_mm": (_i32, [_P, _P, _P, _P, _i32, _P, _P, _P, _P, _P, _P, _P]),
     "rn_conv_weight_pack_i8": (_i32, [_P, _P, _P, _P, _P]),
