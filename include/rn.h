@@ -199,6 +199,34 @@ int rn_conv_bwd_filter_i8(const rn_conv_desc* d, const void* x_codes, const floa
 int rn_conv_bwd_filter_x(const rn_conv_desc* d, const void* x, const void* dy, float* dw, const float* in_scale,
                          const float* in_shift, void* ws, int64_t ws_bytes, rn_stream_t stream);
 
+/* Which weight-gradient kernel rn_conv_bwd_filter / _ws / _x (xf != 0: with an input transform) / _i8 (i8 != 0:
+ * from int8 codes) would launch for d with a workspace of ws_bytes bytes (0: none) under the rn_set_tuning keys
+ * set at this moment, from the launch's own decision tree. No launch and no device call: it answers on a host
+ * without a GPU (where the chip counts as 256 CUs). Returns the family in the low 8 bits (RN_WGRAD_FAMILY) and,
+ * for RN_WGRAD_TILE and the RN_WGRAD_DMA* families, the tile's rows over K (RN_WGRAD_ROWS) and columns over
+ * r s c (RN_WGRAD_COLS); 0 for the others. *splits (nullable): the M splits of that launch (the image splits of
+ * the band kernels, the workgroups of the depthwise one); *slab (nullable): 1 = every split stores its partial
+ * into the workspace and a reduction adds them into dw (<= 16 splits of whole 16-byte chunks: the few-split
+ * reduction unless rn_set_tuning 25 = 1), 0 = fp32 atomics into dw. -1, with rn_last_error untouched and the
+ * out-parameters unwritten, where the launch would be refused.
+ * ws_bytes = 0 stands for a call without a workspace (ws = NULL). A launch given a non-null ws of 0 bytes differs in
+ * one place: the 256-column tiles are chosen on ws != NULL alone, so it runs RN_WGRAD_DMA256 with atomics where this
+ * query, asked with 0, answers RN_WGRAD_DMA128.
+ * RN_WGRAD_DMA64 / 128 / 256: wgrad_big_kernel's 64 x 128, 128 x 128 and 128- or 256-row x 256-column tiles. */
+#define RN_WGRAD_TILE 1
+#define RN_WGRAD_DMA64 2
+#define RN_WGRAD_DMA128 3
+#define RN_WGRAD_DMA256 4
+#define RN_WGRAD_DBAND 5
+#define RN_WGRAD_GBAND 6
+#define RN_WGRAD_STREAM 7
+#define RN_WGRAD_DEPTHWISE 8
+#define RN_WGRAD_FAMILY(v) ((v) & 0xff)
+#define RN_WGRAD_ROWS(v) (((v) >> 8) & 0xfff)
+#define RN_WGRAD_COLS(v) (((v) >> 20) & 0x7ff)
+int32_t rn_conv_wgrad_kernel(const rn_conv_desc* d, int32_t xf, int32_t i8, int64_t ws_bytes, int32_t* splits,
+                             int32_t* slab);
+
 /* Number of fp32 elements of the master weight (K x R x S x c_real/groups, KRSC). */
 int64_t rn_conv_weight_numel(const rn_conv_desc* d);
 
@@ -349,7 +377,9 @@ int rn_stem_prepare_p4(const rn_bn_desc* d, const float* x_nchw, int32_t n, int3
  * layout's r * s * 8), with no in-image tests (the border is zero). d: the conv0 descriptor
  * (c = 8 as for rn_stem_prepare, c_real = 3); hp >= (p-1)*stride_h + 8, wp >= (q-1)*stride_w + 8.
  * w4: [k][8][8][4] from rn_stem_weight_pack_p4 (master [k][r][s][c_real] fp32).
- * rn_stem_conv_wgrad_p4 ADDS dW into dw ([k][r][s][c_real] fp32). */
+ * rn_stem_conv_wgrad_p4 ADDS dW into dw ([k][r][s][c_real] fp32) with fp32 atomics, on the 64 x 128 LDS-DMA tile
+ * (RN_WGRAD_DMA64's kernel; rn_conv_wgrad_kernel does not cover this entry point): 2 column tiles, M = n p q split
+ * into min(256, max(1, mtiles / 8)) parts of whole 64-row M-tiles dealt evenly, mtiles = ceil(M / 64). */
 int32_t rn_stem_p4_supported(const rn_conv_desc* d, int32_t hp, int32_t wp);
 int rn_stem_weight_pack_p4(const rn_conv_desc* d, const float* w_master, void* w4, rn_stream_t stream);
 int rn_stem_conv_fwd_p4(const rn_conv_desc* d, const void* x4, const void* w4, void* y, int32_t hp, int32_t wp,

@@ -5524,18 +5524,38 @@ int rn_conv_bwd_data(const rn_conv_desc* d, const void* dy, const void* w_crsk, 
 }  // extern "C"
 
 namespace {
-// The weight-gradient kernel choice for d. launch == false: only *ws_need (bytes of split-M partial
-// slabs the chosen kernel stores when given a workspace; 0 = it adds into dw with atomics).
+// What wgrad_dispatch chose (rn_conv_wgrad_kernel): the RN_WGRAD_* family, its tile (TILE and the DMA
+// families), the M or image splits of the launch, and whether they go through slabs
+struct WgradRoute {
+  int family, rows, cols;
+  int64_t splits;
+  int slab;
+};
+// The weight-gradient kernel choice for d. launch == false: no launch, no device call and no error message,
+// only the walk of the same predicates over (ws != nullptr, ws_bytes) -- *ws_need (bytes of split-M partial
+// slabs the chosen kernel stores when given a workspace; 0 = it adds into dw with atomics) and *route (the
+// kernel a launch with that workspace would run; -1 where it would be refused).
 // i8: x holds int8 codes, dW = *xunit * sum dy * code (the streaming kernel and the 128 / 256-column
 // LDS-DMA tiles only: rn_conv_wgrad_i8_supported)
 int wgrad_dispatch(const rn_conv_desc* d, const void* x, const void* dy, float* dw, const float* in_scale,
                    const float* in_shift, float* ws, int64_t ws_bytes, int64_t* ws_need, bool launch,
-                   hipStream_t st, const float* xunit = nullptr, bool i8 = false) {
+                   hipStream_t st, const float* xunit = nullptr, bool i8 = false, WgradRoute* route = nullptr) {
   if (ws_need) *ws_need = 0;
-  RN_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "in_scale / in_shift must both be set");
-  RN_CHECK_ARG(!in_scale || d->groups == 1, "input transform on a grouped conv");
-  RN_CHECK_ARG(!i8 || (!in_scale && d->dtype == RN_BF16 && d->groups <= 1 && d->c_real == d->c && d->c % 16 == 0),
+// (a refusal names its reason only at a launch: the plan-time queries leave rn_last_error alone)
+#define RN_WGRAD_ARG(cond, msg)          \
+  do {                                   \
+    if (!(cond)) {                       \
+      if (launch) RN_CHECK_ARG(0, msg);  \
+      return -1;                         \
+    }                                    \
+  } while (0)
+  RN_WGRAD_ARG((in_scale == nullptr) == (in_shift == nullptr), "in_scale / in_shift must both be set");
+  RN_WGRAD_ARG(!in_scale || d->groups == 1, "input transform on a grouped conv");
+  RN_WGRAD_ARG(!i8 || (!in_scale && d->dtype == RN_BF16 && d->groups <= 1 && d->c_real == d->c && d->c % 16 == 0),
                "int8 input codes: bf16 dy, dense, whole 16-channel chunks, no input transform");
+  auto chosen = [&](int family, int rows, int cols, int64_t splits, bool slab) {
+    if (route) *route = WgradRoute{family, rows, cols, splits, slab ? 1 : 0};
+  };
 
   WgradArgs a{};
   a.x = x; a.dy = dy; a.dw = dw;
@@ -5553,17 +5573,18 @@ int wgrad_dispatch(const rn_conv_desc* d, const void* x, const void* dy, float* 
   // depthwise: dwconv_wgrad_kernel, one [c][9] partial per workgroup into the slab (needed in every mode:
   // the kernel has no atomic form)
   if (dw_ok(d) && dw_wgrad_shape(d)) {
-    RN_CHECK_ARG(!in_scale && !i8, "depthwise weight gradient: no input transform, no int8 codes");
+    RN_WGRAD_ARG(!in_scale && !i8, "depthwise weight gradient: no input transform, no int8 codes");
     DwArgs g{};
     const int blocks = dw_geometry(d, 2, g, 2 * wgrad_cus(), kDwWgradThreads);
     const int64_t n = (int64_t)9 * d->c, need = blocks * n * 4;
     if (ws_need) *ws_need = need;
-    if (!launch) return 0;
-    RN_CHECK_ARG((int64_t)d->n * g.pb * g.Q * g.nchunk < INT32_MAX, "depthwise: tensor too large");
+    if (launch || route) RN_WGRAD_ARG((int64_t)d->n * g.pb * g.Q * g.nchunk < INT32_MAX, "depthwise: tensor too large");
     if (!ws || ws_bytes < need) {
-      rn_set_error("deterministic weight gradients need the split-M workspace (rn_conv_wgrad_ws_bytes)");
+      if (launch) rn_set_error("deterministic weight gradients need the split-M workspace (rn_conv_wgrad_ws_bytes)");
       return -1;
     }
+    chosen(RN_WGRAD_DEPTHWISE, 0, 0, blocks, true);
+    if (!launch) return 0;
     g.x = (const bf16_t*)x; g.dy = (const bf16_t*)dy; g.slab = ws;
     if (d->stride_h == 1) hipLaunchKernelGGL(dwconv_wgrad_kernel<1>, dim3(blocks), dim3(kDwWgradThreads), 0, st, g);
     else hipLaunchKernelGGL(dwconv_wgrad_kernel<2>, dim3(blocks), dim3(kDwWgradThreads), 0, st, g);
@@ -5619,7 +5640,7 @@ int wgrad_dispatch(const rn_conv_desc* d, const void* x, const void* dy, float* 
     const int64_t need = split * a.K * (int64_t)a.ldw * 4;
     a.slab = (slab_ok && ws && ws_bytes >= need) ? ws : nullptr;
     if (det && !a.slab) {
-      rn_set_error("deterministic weight gradients need the split-M workspace (rn_conv_wgrad_ws_bytes)");
+      if (launch) rn_set_error("deterministic weight gradients need the split-M workspace (rn_conv_wgrad_ws_bytes)");
       return false;
     }
     return true;
@@ -5643,9 +5664,10 @@ int wgrad_dispatch(const rn_conv_desc* d, const void* x, const void* dy, float* 
     const int64_t want = std::max<int64_t>(1, wgrad_cus() / slices);  // (the slab stays ~ CUs x slice)
     g.ipw = (int)ceil_div(d->n, std::min<int64_t>(d->n, want));
     const int64_t split = ceil_div(d->n, g.ipw);
-    if (!launch) return finish(split, "wgrad_dband");
     if (ws && ws_bytes >= split * a.K * (int64_t)a.ldw * 4) {
       if (!use_slab(split)) return -1;
+      chosen(RN_WGRAD_DBAND, 0, 0, split, true);
+      if (!launch) return finish(split, "wgrad_dband");
       g.slab = a.slab;
       const dim3 grid((unsigned)split, d->c / cs, d->k / ks);
 #define RN_DBAND(XFV)                                                                                            \
@@ -5678,8 +5700,9 @@ int wgrad_dispatch(const rn_conv_desc* d, const void* x, const void* dy, float* 
     const int64_t split = ceil_div(d->n, g.ipw);
     const int64_t need = split * a.K * (int64_t)a.ldw * 4;  // (a.ldw = 9 * channels per group)
     if (ws_need) *ws_need = need;
-    if (!launch) return 0;
     if (ws && ws_bytes >= need) {
+      chosen(RN_WGRAD_GBAND, 0, 0, split, true);
+      if (!launch) return 0;
       g.slab = a.slab = ws;
       const dim3 grid((unsigned)split, slices);
       if (gb == 1) hipLaunchKernelGGL((wgrad_gband_kernel<128, 4, 64, 1, 2>), grid, dim3(512), 0, st, g);
@@ -5701,15 +5724,16 @@ int wgrad_dispatch(const rn_conv_desc* d, const void* x, const void* dy, float* 
       (int64_t)a.M * (d->k + d->c) * 2 < INT32_MAX) {
     const int64_t mtiles = ceil_div(a.M, 64);
     int64_t split = std::min<int64_t>(wgrad_cus(), std::max<int64_t>(1, mtiles / 4));
-    // (at launch: no more splits than the workspace holds -- rn_set_tuning 21 may have changed since the
-    // plan sized it, and the int8-codes form has no other kernel to fall back to)
+    // (no more splits than the workspace holds -- rn_set_tuning 21 may have changed since the plan sized
+    // it, and the int8-codes form has no other kernel to fall back to)
     const int64_t slab1 = (int64_t)a.K * a.ldw * 4;
-    if (launch && ws && ws_bytes >= slab1) split = std::min<int64_t>(split, ws_bytes / slab1);
+    if (ws && ws_bytes >= slab1) split = std::min<int64_t>(split, ws_bytes / slab1);
     a.m_per_split = (int)(ceil_div(mtiles, split) * 64);
     const int64_t nsplit = ceil_div(a.M, a.m_per_split);
-    if (!launch) return finish(nsplit, "wgrad_stream");
     if (ws && ws_bytes >= nsplit * a.K * (int64_t)a.ldw * 4) {
       if (!use_slab(nsplit)) return -1;
+      chosen(RN_WGRAD_STREAM, 0, 0, nsplit, true);
+      if (!launch) return finish(nsplit, "wgrad_stream");
       const dim3 grid((unsigned)nsplit);
       const bool t = in_scale != nullptr;
 #define RN_STREAM(KK, CC)                                                                         \
@@ -5743,8 +5767,9 @@ int wgrad_dispatch(const rn_conv_desc* d, const void* x, const void* dy, float* 
     int64_t split = std::min<int64_t>(std::max<int64_t>(1, 512 / tiles), std::max<int64_t>(1, mtiles / 8));
     a.m_per_split = (int)(ceil_div(mtiles, split) * 64);
     split = ceil_div(a.M, a.m_per_split);
-    if (!launch) return finish(split, "wgrad_dma64");
     if (!use_slab(split)) return -1;
+    chosen(RN_WGRAD_DMA64, 64, 128, split, a.slab != nullptr);
+    if (!launch) return finish(split, "wgrad_dma64");
     hipLaunchKernelGGL((wgrad_big_kernel<64, 3, 128>), dim3((unsigned)(tiles * split)), dim3(256), 0, st, a);
     return finish(split, "wgrad_dma64");
   }
@@ -5771,8 +5796,9 @@ int wgrad_dispatch(const rn_conv_desc* d, const void* x, const void* dy, float* 
     int64_t split = std::min<int64_t>(std::max<int64_t>(1, target / tiles), std::max<int64_t>(1, mtiles / 8));
     a.m_per_split = (int)(ceil_div(mtiles, split) * 64);
     split = ceil_div(a.M, a.m_per_split);
-    if (!launch) return finish(split, "wgrad_dma128");
     if (!use_slab(split)) return -1;
+    chosen(RN_WGRAD_DMA128, 128, 128, split, a.slab != nullptr);
+    if (!launch) return finish(split, "wgrad_dma128");
     const dim3 g128((unsigned)(tiles * split));
 #define RN_W128(DV)                                                                                        \
   if (in_scale) hipLaunchKernelGGL((wgrad_big_kernel<128, 2, 128, 1, 0, DV>), g128, dim3(256), 0, st, a);   \
@@ -5795,8 +5821,9 @@ int wgrad_dispatch(const rn_conv_desc* d, const void* x, const void* dy, float* 
     int64_t split = std::min<int64_t>(std::max<int64_t>(1, wgrad_cus() / tiles), std::max<int64_t>(1, mtiles / 4));
     a.m_per_split = (int)(ceil_div(mtiles, split) * 64);
     split = ceil_div(a.M, a.m_per_split);
-    if (!launch) return finish(split, "wgrad_big");
     if (!use_slab(split)) return -1;
+    chosen(RN_WGRAD_DMA256, bmk, 256, split, a.slab != nullptr);
+    if (!launch) return finish(split, "wgrad_big");
     dim3 grid((unsigned)(tiles * split));
 #define RN_W256(DV)                                                                                              \
   if (in_scale) {                                                                                               \
@@ -5847,10 +5874,12 @@ int wgrad_dispatch(const rn_conv_desc* d, const void* x, const void* dy, float* 
   a.nkt = (int)ceil_div(a.K, bmk);
   dim3 grid((unsigned)(a.nct * a.nkt * split));
   if (det) {  // this register-staged kernel stores slabs only in the deterministic mode
-    if (!launch) return finish(split, "wgrad");
     if (!use_slab(split)) return -1;
+    chosen(RN_WGRAD_TILE, bmk, bnc, split, true);
+    if (!launch) return finish(split, "wgrad");
   } else {
     if (ws_need) *ws_need = 0;
+    chosen(RN_WGRAD_TILE, bmk, bnc, split, false);
     if (!launch) return 0;
     a.slab = nullptr;
   }
@@ -5870,6 +5899,7 @@ int wgrad_dispatch(const rn_conv_desc* d, const void* x, const void* dy, float* 
   }
   if (det) return finish(split, "wgrad");
   return rn_check_launch("wgrad");
+#undef RN_WGRAD_ARG
 }
 }  // namespace
 
@@ -5904,6 +5934,20 @@ int rn_conv_bwd_filter_ws(const rn_conv_desc* d, const void* x, const void* dy, 
 
 int rn_conv_bwd_filter(const rn_conv_desc* d, const void* x, const void* dy, float* dw, rn_stream_t stream) {
   return rn_conv_bwd_filter_x(d, x, dy, dw, nullptr, nullptr, nullptr, 0, stream);
+}
+
+int32_t rn_conv_wgrad_kernel(const rn_conv_desc* d, int32_t xf, int32_t i8, int64_t ws_bytes, int32_t* splits,
+                             int32_t* slab) {
+  if (!d || ws_bytes < 0 || (i8 && !rn_conv_wgrad_i8_supported(d))) return -1;
+  // (nothing is read through these at launch == false: they stand for "a workspace" and "a transform")
+  float* const some = reinterpret_cast<float*>(16);
+  WgradRoute r{};
+  if (wgrad_dispatch(d, nullptr, nullptr, nullptr, xf ? some : nullptr, xf ? some : nullptr, ws_bytes > 0 ? some : nullptr,
+                     ws_bytes, nullptr, false, nullptr, nullptr, i8 != 0, &r) || r.family == 0)
+    return -1;
+  if (splits) *splits = (int32_t)r.splits;
+  if (slab) *slab = r.slab;
+  return r.family | (r.rows << 8) | (r.cols << 20);
 }
 
 int32_t rn_conv_wgrad_i8_supported(const rn_conv_desc* d) {

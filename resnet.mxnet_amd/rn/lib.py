@@ -18,6 +18,9 @@ RN_BF16 = 0
 RN_F32 = 1
 RN_POOL_MAX = 0
 RN_POOL_AVG = 1
+# rn_conv_wgrad_kernel's families (rn.h: RN_WGRAD_*; the tile's rows in bits 8-19, its columns from bit 20)
+(RN_WGRAD_TILE, RN_WGRAD_DMA64, RN_WGRAD_DMA128, RN_WGRAD_DMA256, RN_WGRAD_DBAND, RN_WGRAD_GBAND, RN_WGRAD_STREAM,
+ RN_WGRAD_DEPTHWISE) = range(1, 9)
 
 _P = C.c_void_p
 _i32 = C.c_int32
@@ -83,6 +86,7 @@ SIGNATURES = {
     "rn_conv_bwd_filter": (_i32, [_P, _P, _P, _P, _P]),
     "rn_conv_wgrad_ws_bytes": (_i64, [_P]),
     "rn_conv_bwd_filter_ws": (_i32, [_P, _P, _P, _P, _P, _i64, _P]),
+    "rn_conv_wgrad_kernel": (_i32, [_P, _i32, _i32, _i64, _P, _P]),
     "rn_conv_wgrad_i8_supported": (_i32, [_P]),
     "rn_conv_wgrad_i8_ws_bytes": (_i64, [_P]),
     "rn_conv_bwd_filter_i8": (_i32, [_P, _P, _P, _P, _P, _P, _i64, _P]),

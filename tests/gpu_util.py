@@ -1,4 +1,5 @@
 """Helpers for GPU parity tests: NCHW numpy <-> NHWC device tensors, direct C-ABI calls."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -7,6 +8,19 @@ import torch
 from rn import lib as L
 
 BF16, F32 = L.RN_BF16, L.RN_F32
+TUNE_DEFAULTS = {10: 512, 18: 55, 21: 50}  # every other rn_set_tuning key defaults to 0
+
+
+@contextlib.contextmanager
+def tuning(keys):
+    """rn_set_tuning key: value for the block, every key back at its default after."""
+    try:
+        for key, val in keys.items():
+            L.call("rn_set_tuning", key, val)
+        yield
+    finally:
+        for key in keys:
+            L.call("rn_set_tuning", key, TUNE_DEFAULTS.get(key, 0))
 
 
 def tdt(dtype):

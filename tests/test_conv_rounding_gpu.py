@@ -10,7 +10,6 @@ include/rn.h promises y = sum (+ bias) (+ add_src), accumulated in fp32 and stor
 Each kernel family runs forward, forward + add_src, data gradient, data gradient + add_src into NaN-filled outputs,
 after asserting through the host's own answers (rn_conv_tile, rn_conv_fwd_streamed, rn_conv_dgrad_streamed,
 d.grouped_direct) that the intended kernel runs. The largest ratio per call is printed (DESIGN.md records them)."""
-import contextlib
 import ctypes as C
 
 import numpy as np
@@ -19,25 +18,13 @@ import torch
 
 import rounding_cases as R
 from rn import lib as L
-from gpu_util import BF16, F32, conv_desc, from_nhwc, p, rounding_excess, stream, tdt, to_nhwc
+from gpu_util import BF16, F32, conv_desc, from_nhwc, p, rounding_excess, stream, tdt, to_nhwc, tuning
 
 pytestmark = pytest.mark.gpu
 
 REGIMES = ["gauss", "exact"]
 WAYS = ("fwd", "fwd_add", "dgrad", "dgrad_add")
-TUNE_DEFAULTS = {10: 512, 18: 55}  # every other rn_set_tuning key defaults to 0
 _cid = lambda c: "x".join(map(str, c))
-
-
-@contextlib.contextmanager
-def tuning(keys):
-    try:
-        for key, val in keys.items():
-            L.call("rn_set_tuning", key, val)
-        yield
-    finally:
-        for key in keys:
-            L.call("rn_set_tuning", key, TUNE_DEFAULTS.get(key, 0))
 
 
 def _master(wt, dev):  # [k][r][s][c / groups] fp32

@@ -5,6 +5,9 @@ Tolerances (max |err| / max |ref|):
   bf16 path: 1.5e-2 (oracle fed the same bf16-rounded inputs; output rounded to bf16 = 2^-8)
 That bar passes a truncated store or a partial sum kept in bf16: test_conv_rounding_gpu.py holds every bf16 forward
 and data-gradient kernel to one rounding per element (gpu_util.rounding_excess) and to exact integer sums.
+The weight gradients' 5e-3 of the maximum likewise passes a partial kept in bf16 or a row dropped at a split seam:
+test_wgrad_rounding_gpu.py holds every weight-gradient kernel, in each epilogue and at three or more splits with a
+ragged last one, to the oracle's bits on integer data and to the fp32 rounding bar.
 """
 import ctypes as C
 
@@ -1902,8 +1905,9 @@ def test_wgrad_stream_1x1(gpu, kc, xf):
     stage 1's conv1 / conv3 / shortcut; rn_set_tuning 19 = 0): one streaming pass per workgroup over its M range,
     the split partials through the slab. Plain and with the producing BatchNorm+ReLU applied to x on load
     (rn_conv_bwd_filter_x): against the fp64 oracle of the same (rounded) operands, bit-identical run to
-    run, and equal to the tiled kernels (19 = 1) within fp32 summation-order rounding; a ragged M (the
-    last rows of the last split past the range)."""
+    run, and equal to the tiled kernels (19 = 1) within fp32 summation-order rounding; a ragged M (429 rows =
+    7 M-tiles, fewer than the 8 that two splits take: ONE split, its last rows past the range -- the seams between
+    splits are test_wgrad_rounding_gpu.py's)."""
     k, c = kc
     n, h, w = 3, 13, 11
     rng = np.random.default_rng(11)
