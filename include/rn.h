@@ -538,6 +538,19 @@ int rn_sgd_mom_update_pack(int32_t ntensors, const int64_t* offsets, const int64
                            const rn_wpack* packs, const int32_t* work, int32_t nwork,
                            int32_t lowp_dtype, float lr, const float* lr_dev, float momentum,
                            float rescale_grad, float clip, rn_stream_t stream);
+/* rn_sgd_mom_update / rn_sgd_mom_update_pack with per-tensor learning-rate multipliers (MXNet's
+ * lr_mult): lr_mults, nullable, a device table of one float per tensor; lr_eff = lr * lr_mults[t], one
+ * fp32 product, everything else unchanged. The two entry points above call these with NULL; with NULL,
+ * or every entry 1.0f, the result is bit-identical to theirs. */
+int rn_sgd_mom_update_lrm(int32_t ntensors, const int64_t* offsets, const int64_t* numels,
+                          const float* wds, const float* lr_mults, float* w, const float* g, float* mom,
+                          void* w_lowp, int32_t lowp_dtype, float lr, const float* lr_dev,
+                          float momentum, float rescale_grad, float clip, rn_stream_t stream);
+int rn_sgd_mom_update_pack_lrm(int32_t ntensors, const int64_t* offsets, const int64_t* numels,
+                               const float* wds, const float* lr_mults, float* w, const float* g,
+                               float* mom, const rn_wpack* packs, const int32_t* work, int32_t nwork,
+                               int32_t lowp_dtype, float lr, const float* lr_dev, float momentum,
+                               float rescale_grad, float clip, rn_stream_t stream);
 /* Host helper: fills `work` (host memory, capacity max_items x 4) for the tensors described by
  * numels / packs (host copies); returns the item count, or -1 if max_items is too small. */
 int32_t rn_sgd_pack_work(int32_t ntensors, const int64_t* numels, const rn_wpack* packs, int32_t* work,
@@ -711,6 +724,69 @@ int64_t rn_weight_gdrq_ws_bytes(int32_t count);
  * w_krsc / w_crsk (channels >= c_real, columns >= k) is not written (the buffers start zeroed). */
 int rn_weight_gdrq_pack(const rn_wgdrq_item* items, int32_t count, int32_t dtype, float* ws,
                         rn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * QIL -- quantization-interval learning, mx.sym.Custom(op_type="QIL_PY") (core/graph_optimize.py:
+ * 166-179, core/operator/QIL.py:34-176, the "ste" branch): a pruning point p and a clipping point c,
+ * trainable parameters of shape (1,), DEVICE pointers read by the kernels at run time. Every forward
+ * first clamps them, p := max(p, 0) and c := min(c, 1), and writes the clamped values back. Then,
+ * every operation rounded to fp32 on its own (no contraction):
+ *   center = 0.5 * (c + p); distance = 0.5 * (c - p); alpha = 0.5 / distance;
+ *   beta = (-0.5 * center) / distance + 0.5;
+ *   a = |x|, s = sign(x) (0 at 0); flag = a >= p && a <= c (both ends included);
+ *   t = s where a > c, s * (alpha * a + beta) where flag, else 0;
+ *   q = roundf(t * L) in -L .. L (half away from zero), L = 2^nbits - 1; value = q / (float)L (one
+ *   fp32 division) rounded to the storage type: the output lives in [-1, 1].
+ * Backward, the rounding straight-through: dx = dy * alpha where flag && x != 0, else 0;
+ *   dp = sum flag * dy * s * (a - c) / (c - p)^2;  dc = -sum flag * dy * s * (a - p) / (c - p)^2.
+ * Results are unspecified for p >= c after the clamp (the reference asserts p < c on the host).
+ * ------------------------------------------------------------------------------------- */
+/* Activation forward, one streaming launch, the same in training and inference. out: the values
+ * (nullable only with codes). codes (nullable): the signed int8 q, n a multiple of 16, nbits <= 7
+ * (else -1, nothing launched). unit (nullable): receives 1.0f / L. x / out / codes 16-byte aligned;
+ * any n without codes. */
+int rn_qil_fwd(int32_t dtype, int64_t n, const void* x, float* p, float* c, int32_t nbits, void* out,
+               void* codes, float* unit, rn_stream_t stream);
+/* Workspace of rn_qil_bwd / rn_weight_qil_bwd: two fp32 partials per block of a grid that depends on
+ * n only. */
+int64_t rn_qil_bwd_ws_bytes(int64_t n);
+/* Activation backward: one pass writes dx (+ add_src, nullable; the add in fp32, then rounded) and
+ * one fp32 partial per block for each of the two sums -- per element only dy * s * (a - c) and
+ * dy * s * (a - p) are formed, a thread adding its elements in index order, the wave butterfly, the
+ * four waves through the LDS --; a second small launch adds the partials in index order (32
+ * consecutive partials per lane of one wave, then the 64 lane sums in lane order, as rn_pact_bwd),
+ * divides by (c - p) * (c - p) once and WRITES dp[0] and dc[0]. No atomics: bit-identical from run to
+ * run. dx may alias dy or add_src. ws: rn_qil_bwd_ws_bytes(n). 16-byte aligned pointers; any n. */
+int rn_qil_bwd(int32_t dtype, int64_t n, const void* x, const void* dy, const float* p, const float* c,
+               void* dx, const void* add_src, float* dp, float* dc, void* ws, rn_stream_t stream);
+/* One weight of rn_weight_qil_pack: the fp32 master (KRSC, c_real channels) of a QIL weight and the
+ * copies written from it. */
+typedef struct rn_wqil_item {
+  const float* master; /* k * rs * c_real fp32                                              */
+  float* qw;           /* fake-quantized copy q / L, master layout (required)               */
+  float* unit;         /* nullable: 1 / L                                                   */
+  float* p;            /* the pruning point: clamped to >= 0 and written back               */
+  float* c;            /* the clipping point: clamped to <= 1 and written back              */
+  int8_t* w_codes;     /* nullable: int8 q in -L .. L, KRSC, channel stride c               */
+  void* w_krsc;        /* nullable: forward compute copy of qw, KRSC with channel stride c
+                        * (rn_conv_weight_pack's w_krsc), dtype of the call                 */
+  void* w_crsk;        /* nullable: data-gradient compute copy of qw, dense CRSK with k_pad
+                        * stride (rn_conv_weight_pack's w_crsk), dtype of the call          */
+  int32_t k, rs, c_real, c_stride, k_pad, nbits;
+} rn_wqil_item;
+/* Workspace of rn_weight_qil_pack: the four coefficients of each of count weights. */
+int64_t rn_weight_qil_ws_bytes(int32_t count);
+/* Every QIL weight of a network in two launches: per weight the clamp write-back, the unit and the
+ * coefficients, then the copies. items: DEVICE array of count entries; ws:
+ * rn_weight_qil_ws_bytes(count). The padding of w_codes / w_krsc / w_crsk (channels >= c_real,
+ * columns >= k) is not written (the buffers start zeroed). */
+int rn_weight_qil_pack(const rn_wqil_item* items, int32_t count, int32_t dtype, float* ws,
+                       rn_stream_t stream);
+/* Backward of a QIL weight over the fp32 gradient dw of its master w (n elements, the same layout),
+ * in place: dw *= alpha * flag * [w != 0]; dp / dc from the gradient as it came in, by rn_qil_bwd's
+ * two launches and reduction rules. ws: rn_qil_bwd_ws_bytes(n). w / dw 16-byte aligned. */
+int rn_weight_qil_bwd(int64_t n, const float* w, float* dw, const float* p, const float* c, float* dp,
+                      float* dc, void* ws, rn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Runtime.

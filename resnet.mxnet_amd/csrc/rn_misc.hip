@@ -277,13 +277,15 @@ __global__ void col_sum_kernel(int64_t m, int c, int ld, const T* __restrict__ x
 // ------------------------------------------------------------------------------ SGD
 template <typename LT>
 __global__ void sgd_mom_kernel(const int64_t* __restrict__ offs, const int64_t* __restrict__ numels,
-                               const float* __restrict__ wds, float* __restrict__ w, const float* __restrict__ g,
-                               float* __restrict__ mom, LT* __restrict__ wl, float lr, const float* lr_dev,
-                               float momentum, float rescale, float clip) {
+                               const float* __restrict__ wds, const float* __restrict__ lrms, float* __restrict__ w,
+                               const float* __restrict__ g, float* __restrict__ mom, LT* __restrict__ wl, float lr,
+                               const float* lr_dev, float momentum, float rescale, float clip) {
   const int t = blockIdx.y;
   const int64_t off = offs[t], n = numels[t];
   const float wd = wds[t];
-  const float lrv = lr_dev ? *lr_dev : lr;
+  // (lr_mult: one fp32 product per tensor; without a table the step is the plain lr, bit for bit)
+  const float lr0 = lr_dev ? *lr_dev : lr;
+  const float lrv = lrms ? lr0 * lrms[t] : lr0;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t k = off + i;
     float gr = rescale * g[k];
@@ -306,7 +308,8 @@ __global__ void sgd_mom_kernel(const int64_t* __restrict__ offs, const int64_t* 
 constexpr int kSgdChunk = 4096;
 template <typename LT, bool CHECK = false>
 __global__ __launch_bounds__(256) void sgd_mom_pack_kernel(const int64_t* __restrict__ offs,
-                                                           const float* __restrict__ wds, float* __restrict__ w,
+                                                           const float* __restrict__ wds,
+                                                           const float* __restrict__ lrms, float* __restrict__ w,
                                                            const float* __restrict__ g, float* __restrict__ mom,
                                                            const rn_wpack* __restrict__ packs,
                                                            const int4* __restrict__ work, const int64_t* numels,
@@ -318,7 +321,8 @@ __global__ __launch_bounds__(256) void sgd_mom_pack_kernel(const int64_t* __rest
   const int t = wi.x;
   const int64_t off = offs[t];
   const float wd = wds[t];
-  const float lrv = lr_dev ? *lr_dev : lr;
+  const float lr0 = lr_dev ? *lr_dev : lr;
+  const float lrv = lrms ? lr0 * lrms[t] : lr0;
   const rn_wpack pk = packs[t];
   LT* __restrict__ wk = reinterpret_cast<LT*>(pk.krsc);
   LT* __restrict__ wc = reinterpret_cast<LT*>(pk.crsk);
@@ -831,6 +835,188 @@ __global__ __launch_bounds__(256) void gdrq_bwd_kernel(int64_t n, const T* __res
   }
 }
 
+// ---- QIL (core/operator/QIL.py:34-176, QIL_PY, the "ste" branch): a pruning point p and a clipping point c,
+// both trainable and read from device memory by every launch. |x| below p goes to 0, above c to +-1, the interval
+// between them linearly onto [0, 1]; then the grid of L = 2^nbits - 1 steps: the output lives in [-1, 1].
+// Every operation of the coefficients and of an element's transform is rounded to fp32 on its own (no contraction:
+// the restatements in the tests apply them one by one).
+struct QilCoef {
+  float p, c, alpha, beta;
+};
+__device__ __forceinline__ QilCoef qil_coef(float p, float c) {
+#pragma clang fp contract(off)
+  QilCoef k;
+  k.p = p < 0.f ? 0.f : p;  // the reference's in-place clamp (QIL.py:49-52)
+  k.c = c > 1.f ? 1.f : c;
+  const float center = 0.5f * (k.c + k.p);
+  const float distance = 0.5f * (k.c - k.p);
+  k.alpha = 0.5f / distance;
+  const float nh = -0.5f * center;
+  k.beta = nh / distance + 0.5f;
+  return k;
+}
+// q = roundf(t * L), half away from zero, -L .. L
+__device__ __forceinline__ float qil_code(float x, const QilCoef k, float levels) {
+#pragma clang fp contract(off)
+  const float a = fabsf(x);
+  const float s = (float)((x > 0.f) - (x < 0.f));
+  const float lin = k.alpha * a;
+  const float m = a > k.c ? 1.f : ((a >= k.p && a <= k.c) ? lin + k.beta : 0.f);
+  const float t = s * m;
+  return roundf(t * levels);
+}
+// the clamped points go back to the parameters (one thread of the launch; every thread clamps what it reads, so
+// it does not matter to a reader whether it sees the value from before or after this store)
+__device__ __forceinline__ void qil_write_back(float* p, float* c, const QilCoef k, float levels, float* unit_out) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (*p != k.p) *p = k.p;
+    if (*c != k.c) *c = k.c;
+    if (unit_out) *unit_out = 1.0f / levels;
+  }
+}
+// the values only: 16-byte chunks, then the tail (any n)
+template <typename T>
+__global__ __launch_bounds__(256) void qil_values_kernel(int64_t n, const T* __restrict__ x, T* __restrict__ out,
+                                                         float* p, float* c, float levels,
+                                                         float* __restrict__ unit_out) {
+  const QilCoef k = qil_coef(*p, *c);
+  qil_write_back(p, c, k, levels, unit_out);
+  constexpr int CE = 16 / sizeof(T);
+  const int64_t nc = n / CE;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nc; i += (int64_t)gridDim.x * blockDim.x) {
+    float f[CE];
+    chunk_to_f(reinterpret_cast<const uint4*>(x)[i], f, (const T*)nullptr);
+#pragma unroll
+    for (int e = 0; e < CE; ++e) f[e] = qil_code(f[e], k, levels) / levels;
+    reinterpret_cast<uint4*>(out)[i] = f_to_chunk(f, (const T*)nullptr);
+  }
+  for (int64_t i = nc * CE + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = from_f<T>(qil_code(to_f(x[i]), k, levels) / levels);
+}
+// the values (out nullable) AND their signed int8 codes -L .. L (nbits <= 7), 16 elements (one 16-byte code
+// chunk) per thread as pact_codes_kernel
+template <typename T>
+__global__ __launch_bounds__(256) void qil_codes_kernel(int64_t nchunk, const T* __restrict__ x, T* __restrict__ out,
+                                                        int8_t* __restrict__ codes, float* p, float* c, float levels,
+                                                        float* __restrict__ unit_out) {
+  const QilCoef k = qil_coef(*p, *c);
+  qil_write_back(p, c, k, levels, unit_out);
+  constexpr int CE = 16 / sizeof(T);
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nchunk; i += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t cw[4];
+#pragma unroll
+    for (int h = 0; h < 16 / CE; ++h) {
+      float f[CE];
+      chunk_to_f(reinterpret_cast<const uint4*>(x)[i * (16 / CE) + h], f, (const T*)nullptr);
+#pragma unroll
+      for (int e = 0; e < CE; ++e) {
+        const float q = qil_code(f[e], k, levels);
+        f[e] = q / levels;
+        const int j = h * CE + e;
+        const uint32_t b = (uint32_t)(uint8_t)(int8_t)(int)q;
+        if ((j & 3) == 0) cw[j >> 2] = b;
+        else cw[j >> 2] |= b << (8 * (j & 3));
+      }
+      if (out) reinterpret_cast<uint4*>(out)[i * (16 / CE) + h] = f_to_chunk(f, (const T*)nullptr);
+    }
+    reinterpret_cast<uint4*>(codes)[i] = make_uint4(cw[0], cw[1], cw[2], cw[3]);
+  }
+}
+// backward: dx = dy * alpha where p <= |x| <= c and x != 0, else 0 (+ add, in fp32, then rounded), and the block's
+// share of the two sums  sum dy * s * (|x| - c)  and  sum dy * s * (|x| - p)  over the elements of the interval
+// (dy * s is exact; the difference and the product are rounded once each): per-thread sums in element order, the
+// wave butterfly, the four waves through LDS, one partial per block and sum at part[block] and part[nblk + block]
+// -- pact_bwd_kernel's geometry, no atomics. dx may alias dy or add (each thread reads its elements before it
+// writes them). A weight's backward is the fp32 form with x = w and dx = dy = dw (rn_weight_qil_bwd).
+constexpr int kQilBwdMaxBlocks = 2048;
+static inline int qil_bwd_blocks(int64_t n) {  // a function of n only (rn_qil_bwd_ws_bytes)
+  return (int)std::min<int64_t>(std::max<int64_t>((n + 2047) / 2048, 1), kQilBwdMaxBlocks);
+}
+__device__ __forceinline__ float qil_bwd_elem(float x, float d, const QilCoef k, float& sp, float& sc) {
+#pragma clang fp contract(off)
+  const float a = fabsf(x);
+  const bool flag = a >= k.p && a <= k.c;
+  const float ds = x > 0.f ? d : (x < 0.f ? -d : 0.f);
+  const float tp = ds * (a - k.c);
+  const float tc = ds * (a - k.p);
+  sp += flag ? tp : 0.f;
+  sc += flag ? tc : 0.f;
+  return (flag && x != 0.f) ? d * k.alpha : 0.f;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void qil_bwd_kernel(int64_t n, const T* __restrict__ x, const T* dy, T* dx,
+                                                      const float* __restrict__ p, const float* __restrict__ c,
+                                                      const T* add, float* __restrict__ part) {
+  const QilCoef k = qil_coef(*p, *c);
+  constexpr int CE = 16 / sizeof(T);
+  const int64_t nc = n / CE;  // 16-byte chunks, then the tail
+  float sp = 0.f, sc = 0.f;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nc; i += (int64_t)gridDim.x * blockDim.x) {
+    float fx[CE], fd[CE], fa[CE];
+    chunk_to_f(reinterpret_cast<const uint4*>(x)[i], fx, (const T*)nullptr);
+    chunk_to_f(reinterpret_cast<const uint4*>(dy)[i], fd, (const T*)nullptr);
+    if (add) chunk_to_f(reinterpret_cast<const uint4*>(add)[i], fa, (const T*)nullptr);
+#pragma unroll
+    for (int e = 0; e < CE; ++e) {
+      const float v = qil_bwd_elem(fx[e], fd[e], k, sp, sc);
+      fd[e] = add ? v + fa[e] : v;
+    }
+    reinterpret_cast<uint4*>(dx)[i] = f_to_chunk(fd, (const T*)nullptr);
+  }
+  for (int64_t i = nc * CE + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float v = qil_bwd_elem(to_f(x[i]), to_f(dy[i]), k, sp, sc);
+    if (add) v += to_f(add[i]);
+    dx[i] = from_f<T>(v);
+  }
+  sp = wave_sum(sp);
+  sc = wave_sum(sc);
+  __shared__ float ws[2][4];
+  if ((threadIdx.x & 63) == 0) {
+    ws[0][threadIdx.x >> 6] = sp;
+    ws[1][threadIdx.x >> 6] = sc;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = (ws[0][0] + ws[0][1]) + (ws[0][2] + ws[0][3]);
+    part[gridDim.x + blockIdx.x] = (ws[1][0] + ws[1][1]) + (ws[1][2] + ws[1][3]);
+  }
+}
+// the block partials of both sums added in index order in pact_dgamma_kernel's fixed two-level shape (wave 0: the
+// first sum, wave 1: the second; 32 consecutive partials per lane, then the 64 lane sums in lane order), then the
+// factor 1 / (c - p)^2 once: d = c - p, dp = S_p / (d * d), dc = -(S_c / (d * d)), each operation rounded on its
+// own. dp[0] and dc[0] are written, not accumulated
+__global__ __launch_bounds__(128) void qil_dpc_kernel(const float* __restrict__ part, int nblk,
+                                                      const float* __restrict__ p, const float* __restrict__ c,
+                                                      float* __restrict__ dp, float* __restrict__ dc) {
+  static_assert(kQilBwdMaxBlocks == 64 * 32, "one wave per sum, 32 partials per lane");
+  const int lane = threadIdx.x & 63, which = threadIdx.x >> 6;
+  const float* src = part + (int64_t)which * nblk;
+  float v[32];
+#pragma unroll
+  for (int j = 0; j < 32; ++j) {
+    const int i = lane * 32 + j;
+    v[j] = i < nblk ? src[i] : 0.f;
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < 32; ++j) s += v[j];
+  __shared__ float ls[2][64];
+  ls[which][lane] = s;
+  __syncthreads();
+  if (lane == 0) {
+#pragma clang fp contract(off)
+    float t = 0.f;
+#pragma unroll
+    for (int l = 0; l < 64; ++l) t += ls[which][l];
+    const QilCoef k = qil_coef(*p, *c);
+    const float d = k.c - k.p;
+    const float d2 = d * d;
+    const float r = t / d2;
+    if (which == 0) *dp = r;
+    else *dc = -r;
+  }
+}
+
 // ---- Quantization_int8 of a BatchNorm(+ReLU) output, the BatchNorm applied on load
 // (rn_quant_int8_fwd_codes_bn). Thread = one 16-channel group (one 16-byte code chunk) of the rows
 // r0 + tr, r0 + tr + rl, ...; y = [relu](fmaf(x, scale, shift)) rounded to T exactly as bn_apply_kernel
@@ -1195,6 +1381,69 @@ __global__ __launch_bounds__(256) void wgdrq_pack_kernel(const rn_wgdrq_item* __
   }
 }
 
+// ---- batched QIL weight quantization (rn_weight_qil_pack)
+// one thread per weight: the clamp written back to the two parameters, the unit 1 / L, and the coefficients the
+// pack reads, left at ws[4 * weight ..]
+__global__ void wqil_state_kernel(const rn_wqil_item* __restrict__ items, int count, float* __restrict__ ws) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= count) return;
+  const rn_wqil_item it = items[j];
+  const QilCoef k = qil_coef(it.p[0], it.c[0]);
+  it.p[0] = k.p;
+  it.c[0] = k.c;
+  ws[4 * j + 0] = k.p;
+  ws[4 * j + 1] = k.c;
+  ws[4 * j + 2] = k.alpha;
+  ws[4 * j + 3] = k.beta;
+  if (it.unit) it.unit[0] = 1.0f / (float)((1 << it.nbits) - 1);
+}
+// One read of the master per weight (blockIdx.y), in wgdrq_pack_kernel's 64(k) x 64(c) tiles of one tap: each
+// element's q computed once; the fake-quantized copy q / L, the int8 codes and the forward copy stored in master
+// (KRSC) order, the data-gradient copy (CRSK) transposed through LDS
+template <typename T>
+__global__ __launch_bounds__(256) void wqil_pack_kernel(const rn_wqil_item* __restrict__ items,
+                                                        const float* __restrict__ ws) {
+  __shared__ float tile[64][65];
+  const rn_wqil_item it = items[blockIdx.y];
+  QilCoef kc;
+  kc.p = ws[4 * blockIdx.y + 0];
+  kc.c = ws[4 * blockIdx.y + 1];
+  kc.alpha = ws[4 * blockIdx.y + 2];
+  kc.beta = ws[4 * blockIdx.y + 3];
+  const float levels = (float)((1 << it.nbits) - 1);
+  const int RS = it.rs, cr = it.c_real, K = it.k;
+  const int kt = (K + 63) / 64, ct = (cr + 63) / 64;
+  const int ntiles = kt * RS * ct;
+  T* __restrict__ fwd = reinterpret_cast<T*>(it.w_krsc);
+  T* __restrict__ out = reinterpret_cast<T*>(it.w_crsk);
+  const int cl = threadIdx.x & 63, r0 = threadIdx.x >> 6;
+  for (int tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
+    const int c0 = (tl % ct) * 64, rest = tl / ct;
+    const int tap = rest % RS, k0 = (rest / RS) * 64;
+#pragma unroll 4
+    for (int j = 0; j < 16; ++j) {  // rows k0 + r, columns c0 + cl: coalesced over c
+      const int r = r0 + 4 * j, k = k0 + r, ci = c0 + cl;
+      if (k < K && ci < cr) {
+        const int64_t kt_ = (int64_t)k * RS + tap;
+        const float q = qil_code(it.master[kt_ * cr + ci], kc, levels);
+        const float v = q / levels;
+        it.qw[kt_ * cr + ci] = v;
+        if (it.w_codes) it.w_codes[kt_ * it.c_stride + ci] = (int8_t)(int)q;
+        if (fwd) fwd[kt_ * it.c_stride + ci] = from_f<T>(v);
+        tile[r][cl] = v;
+      }
+    }
+    if (!out) continue;  // (uniform over the block)
+    __syncthreads();
+#pragma unroll 4
+    for (int j = 0; j < 16; ++j) {  // rows c, columns k: coalesced over k
+      const int r = r0 + 4 * j, ci = c0 + r, k = k0 + cl;
+      if (k < K && ci < cr) out[((int64_t)ci * RS + tap) * it.k_pad + k] = from_f<T>(tile[cl][r]);
+    }
+    __syncthreads();
+  }
+}
+
 // the threshold states of NQ quantizers of one tensor from its max (consumed and re-zeroed)
 __global__ void quant_state_multi_kernel(float* __restrict__ curmax, float* minmax0, float* minmax1, int nq,
                                          int is_train, float decay0, float decay1, int first, float* __restrict__ thr) {
@@ -1493,37 +1742,53 @@ int rn_col_sum(int32_t dtype, int64_t m, int32_t c, int32_t ld, const void* x, f
   return rn_check_launch("col_sum");
 }
 
-int rn_sgd_mom_update(int32_t ntensors, const int64_t* offsets, const int64_t* numels, const float* wds, float* w,
-                      const float* g, float* mom, void* w_lowp, int32_t lowp_dtype, float lr, const float* lr_dev,
-                      float momentum, float rescale_grad, float clip, rn_stream_t stream) {
+int rn_sgd_mom_update_lrm(int32_t ntensors, const int64_t* offsets, const int64_t* numels, const float* wds,
+                          const float* lr_mults, float* w, const float* g, float* mom, void* w_lowp,
+                          int32_t lowp_dtype, float lr, const float* lr_dev, float momentum, float rescale_grad,
+                          float clip, rn_stream_t stream) {
   RN_CHECK_ARG(ntensors > 0 && offsets && numels && wds && w && g && mom, "bad arguments");
   RN_CHECK_ARG(ntensors <= 65535, "too many tensors");
   hipStream_t st = as_stream(stream);
   dim3 grid(64, ntensors);
   if (w_lowp && lowp_dtype == RN_BF16)
-    hipLaunchKernelGGL(sgd_mom_kernel<bf16_t>, grid, dim3(256), 0, st, offsets, numels, wds, w, g, mom,
+    hipLaunchKernelGGL(sgd_mom_kernel<bf16_t>, grid, dim3(256), 0, st, offsets, numels, wds, lr_mults, w, g, mom,
                        (bf16_t*)w_lowp, lr, lr_dev, momentum, rescale_grad, clip);
   else
-    hipLaunchKernelGGL(sgd_mom_kernel<float>, grid, dim3(256), 0, st, offsets, numels, wds, w, g, mom,
+    hipLaunchKernelGGL(sgd_mom_kernel<float>, grid, dim3(256), 0, st, offsets, numels, wds, lr_mults, w, g, mom,
                        (float*)w_lowp, lr, lr_dev, momentum, rescale_grad, clip);
   return rn_check_launch("sgd_mom_update");
+}
+
+int rn_sgd_mom_update(int32_t ntensors, const int64_t* offsets, const int64_t* numels, const float* wds, float* w,
+                      const float* g, float* mom, void* w_lowp, int32_t lowp_dtype, float lr, const float* lr_dev,
+                      float momentum, float rescale_grad, float clip, rn_stream_t stream) {
+  return rn_sgd_mom_update_lrm(ntensors, offsets, numels, wds, nullptr, w, g, mom, w_lowp, lowp_dtype, lr, lr_dev,
+                               momentum, rescale_grad, clip, stream);
+}
+
+int rn_sgd_mom_update_pack_lrm(int32_t ntensors, const int64_t* offsets, const int64_t* numels, const float* wds,
+                               const float* lr_mults, float* w, const float* g, float* mom, const rn_wpack* packs,
+                               const int32_t* work, int32_t nwork, int32_t lowp_dtype, float lr, const float* lr_dev,
+                               float momentum, float rescale_grad, float clip, rn_stream_t stream) {
+  RN_CHECK_ARG(ntensors > 0 && offsets && numels && wds && w && g && mom && packs && work && nwork > 0,
+               "bad arguments");
+  hipStream_t st = as_stream(stream);
+  const int4* wk = reinterpret_cast<const int4*>(work);
+  if (lowp_dtype == RN_BF16)
+    hipLaunchKernelGGL(sgd_mom_pack_kernel<bf16_t>, dim3(nwork), dim3(256), 0, st, offsets, wds, lr_mults, w, g, mom,
+                       packs, wk, numels, lr, lr_dev, momentum, rescale_grad, clip);
+  else
+    hipLaunchKernelGGL(sgd_mom_pack_kernel<float>, dim3(nwork), dim3(256), 0, st, offsets, wds, lr_mults, w, g, mom,
+                       packs, wk, numels, lr, lr_dev, momentum, rescale_grad, clip);
+  return rn_check_launch("sgd_mom_update_pack");
 }
 
 int rn_sgd_mom_update_pack(int32_t ntensors, const int64_t* offsets, const int64_t* numels, const float* wds,
                            float* w, const float* g, float* mom, const rn_wpack* packs, const int32_t* work,
                            int32_t nwork, int32_t lowp_dtype, float lr, const float* lr_dev, float momentum,
                            float rescale_grad, float clip, rn_stream_t stream) {
-  RN_CHECK_ARG(ntensors > 0 && offsets && numels && wds && w && g && mom && packs && work && nwork > 0,
-               "bad arguments");
-  hipStream_t st = as_stream(stream);
-  const int4* wk = reinterpret_cast<const int4*>(work);
-  if (lowp_dtype == RN_BF16)
-    hipLaunchKernelGGL(sgd_mom_pack_kernel<bf16_t>, dim3(nwork), dim3(256), 0, st, offsets, wds, w, g, mom, packs, wk,
-                       numels, lr, lr_dev, momentum, rescale_grad, clip);
-  else
-    hipLaunchKernelGGL(sgd_mom_pack_kernel<float>, dim3(nwork), dim3(256), 0, st, offsets, wds, w, g, mom, packs, wk,
-                       numels, lr, lr_dev, momentum, rescale_grad, clip);
-  return rn_check_launch("sgd_mom_update_pack");
+  return rn_sgd_mom_update_pack_lrm(ntensors, offsets, numels, wds, nullptr, w, g, mom, packs, work, nwork, lowp_dtype,
+                                    lr, lr_dev, momentum, rescale_grad, clip, stream);
 }
 
 #if RN_DIAG
@@ -1537,11 +1802,13 @@ int rn_sgd_mom_update_pack_checked(int32_t ntensors, const int64_t* offsets, con
   hipStream_t st = as_stream(stream);
   const int4* wk = reinterpret_cast<const int4*>(work);
   if (lowp_dtype == RN_BF16)
-    hipLaunchKernelGGL((sgd_mom_pack_kernel<bf16_t, true>), dim3(nwork), dim3(256), 0, st, offsets, wds, w, g, mom,
-                       packs, wk, numels, lr, nullptr, momentum, rescale_grad, -1.f, lim, flag);
+    hipLaunchKernelGGL((sgd_mom_pack_kernel<bf16_t, true>), dim3(nwork), dim3(256), 0, st, offsets, wds,
+                       (const float*)nullptr, w, g, mom, packs, wk, numels, lr, nullptr, momentum, rescale_grad, -1.f,
+                       lim, flag);
   else
-    hipLaunchKernelGGL((sgd_mom_pack_kernel<float, true>), dim3(nwork), dim3(256), 0, st, offsets, wds, w, g, mom,
-                       packs, wk, numels, lr, nullptr, momentum, rescale_grad, -1.f, lim, flag);
+    hipLaunchKernelGGL((sgd_mom_pack_kernel<float, true>), dim3(nwork), dim3(256), 0, st, offsets, wds,
+                       (const float*)nullptr, w, g, mom, packs, wk, numels, lr, nullptr, momentum, rescale_grad, -1.f,
+                       lim, flag);
   return rn_check_launch("sgd_mom_update_pack_checked");
 }
 #endif  // RN_DIAG
@@ -1976,6 +2243,77 @@ int rn_weight_gdrq_pack(const rn_wgdrq_item* items, int32_t count, int32_t dtype
   else
     hipLaunchKernelGGL(wgdrq_pack_kernel<float>, dim3(256, count), dim3(256), 0, st, items, count, ws);
   return rn_check_launch("weight_gdrq_pack");
+}
+
+int rn_qil_fwd(int32_t dtype, int64_t n, const void* x, float* p, float* c, int32_t nbits, void* out, void* codes,
+               float* unit, rn_stream_t stream) {
+  RN_CHECK_ARG(x && p && c && n > 0 && (out || codes), "bad arguments");
+  RN_CHECK_ARG(dtype == RN_BF16 || dtype == RN_F32, "bad dtype");
+  RN_CHECK_ARG(nbits >= 1 && nbits <= 16, "bad nbits");
+  RN_CHECK_ARG(!codes || nbits <= 7, "int8 codes need nbits <= 7 (codes up to 2^nbits - 1 must fit a signed byte)");
+  RN_CHECK_ARG(!codes || n % 16 == 0, "int8 codes: n must be a multiple of 16");
+  RN_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)codes & 15) == 0,
+               "16-byte aligned x / out / codes");
+  hipStream_t st = as_stream(stream);
+  const float levels = (float)((1 << nbits) - 1);
+  if (codes) {
+    const int64_t nc = n / 16;
+    if (dtype == RN_BF16)
+      hipLaunchKernelGGL(qil_codes_kernel<bf16_t>, dim3(grid1d(nc)), dim3(256), 0, st, nc, (const bf16_t*)x,
+                         (bf16_t*)out, (int8_t*)codes, p, c, levels, unit);
+    else
+      hipLaunchKernelGGL(qil_codes_kernel<float>, dim3(grid1d(nc)), dim3(256), 0, st, nc, (const float*)x,
+                         (float*)out, (int8_t*)codes, p, c, levels, unit);
+  } else {
+    const int64_t nc = n / (dtype == RN_BF16 ? 8 : 4) + 1;
+    if (dtype == RN_BF16)
+      hipLaunchKernelGGL(qil_values_kernel<bf16_t>, dim3(grid1d(nc)), dim3(256), 0, st, n, (const bf16_t*)x,
+                         (bf16_t*)out, p, c, levels, unit);
+    else
+      hipLaunchKernelGGL(qil_values_kernel<float>, dim3(grid1d(nc)), dim3(256), 0, st, n, (const float*)x,
+                         (float*)out, p, c, levels, unit);
+  }
+  return rn_check_launch("qil_fwd");
+}
+
+int64_t rn_qil_bwd_ws_bytes(int64_t n) { return n > 0 ? (int64_t)sizeof(float) * 2 * qil_bwd_blocks(n) : 0; }
+
+int rn_qil_bwd(int32_t dtype, int64_t n, const void* x, const void* dy, const float* p, const float* c, void* dx,
+               const void* add_src, float* dp, float* dc, void* ws, rn_stream_t stream) {
+  RN_CHECK_ARG(x && dy && p && c && dx && dp && dc && ws && n > 0, "bad arguments");
+  RN_CHECK_ARG(dtype == RN_BF16 || dtype == RN_F32, "bad dtype");
+  RN_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)dx & 15) == 0 &&
+                   ((uintptr_t)add_src & 15) == 0, "16-byte aligned x / dy / dx / add_src");
+  hipStream_t st = as_stream(stream);
+  const int nblk = qil_bwd_blocks(n);
+  if (dtype == RN_BF16)
+    hipLaunchKernelGGL(qil_bwd_kernel<bf16_t>, dim3(nblk), dim3(256), 0, st, n, (const bf16_t*)x, (const bf16_t*)dy,
+                       (bf16_t*)dx, p, c, (const bf16_t*)add_src, (float*)ws);
+  else
+    hipLaunchKernelGGL(qil_bwd_kernel<float>, dim3(nblk), dim3(256), 0, st, n, (const float*)x, (const float*)dy,
+                       (float*)dx, p, c, (const float*)add_src, (float*)ws);
+  hipLaunchKernelGGL(qil_dpc_kernel, dim3(1), dim3(128), 0, st, (const float*)ws, nblk, p, c, dp, dc);
+  return rn_check_launch("qil_bwd");
+}
+
+int64_t rn_weight_qil_ws_bytes(int32_t count) { return count > 0 ? (int64_t)sizeof(float) * 4 * count : 0; }
+
+int rn_weight_qil_pack(const rn_wqil_item* items, int32_t count, int32_t dtype, float* ws, rn_stream_t stream) {
+  RN_CHECK_ARG(items && ws && count > 0 && count <= 65535, "bad arguments");
+  RN_CHECK_ARG(dtype == RN_BF16 || dtype == RN_F32, "bad dtype");
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(wqil_state_kernel, dim3((count + 63) / 64), dim3(64), 0, st, items, count, ws);
+  if (dtype == RN_BF16)
+    hipLaunchKernelGGL(wqil_pack_kernel<bf16_t>, dim3(256, count), dim3(256), 0, st, items, (const float*)ws);
+  else
+    hipLaunchKernelGGL(wqil_pack_kernel<float>, dim3(256, count), dim3(256), 0, st, items, (const float*)ws);
+  return rn_check_launch("weight_qil_pack");
+}
+
+int rn_weight_qil_bwd(int64_t n, const float* w, float* dw, const float* p, const float* c, float* dp, float* dc,
+                      void* ws, rn_stream_t stream) {
+  RN_CHECK_ARG(w && dw && n > 0, "bad arguments");
+  return rn_qil_bwd(RN_F32, n, w, dw, p, c, dw, nullptr, dp, dc, ws, stream);
 }
 
 }  // extern "C"

@@ -299,6 +299,12 @@ class Module:
         params.setdefault("rescale_grad", 1.0 / batch)
         idx2name = {i: n for i, n in enumerate(self._exec.plan.param_names)}
         self._optimizer = opt.create(optimizer, param_idx2name=idx2name, **params)
+        # MXNet's Optimizer.set_lr_mult / set_wd_mult (Module.init_optimizer passes sym=): the variables'
+        # __lr_mult__ / __wd_mult__ reach the update of either executor
+        from rn.plan import multipliers
+        o = self._optimizer
+        o.lr_mult, o.wd_mult = multipliers(self._symbol, self._exec.plan.param_names)
+        self._exec.set_multipliers(o.lr_mult, o.wd_mult)
         if kv is not None:
             kv.set_optimizer(self._optimizer)
         d = _dist()

@@ -400,6 +400,9 @@ def make_module_class(Module):
             known = self._known()
             idx2name = dict(enumerate(a for a in self._symbol.list_arguments() if a not in known))
             self._optimizer = opt.create(optimizer, param_idx2name=idx2name, **params)
+            # (each worker's own init_optimizer hands the same multipliers to its executor)
+            from rn.plan import multipliers
+            self._optimizer.lr_mult, self._optimizer.wd_mult = multipliers(self._symbol, list(idx2name.values()))
             if kv is not None:
                 kv.set_optimizer(self._optimizer)
             self._group.call("init_optimizer", "dist_sync_device")

@@ -6,8 +6,11 @@ to succeed. Executing a Python CustomOp inside the MI355X plan is not supported:
 registration surface. mx.sym.Custom asks the prop registered under its op_type for list_arguments(),
 list_auxiliary_states() and infer_shape() only (symbol.py), so that Custom(data=, gamma=, nbits="4",
 op_type="PACT_PY") gets its gamma input and Custom(data=, alpha=, op_type="GDRQ_PY") its auxiliary alpha;
-a PACT_PY / GDRQ_PY node lowers to the runtime's own PACT / GDRQ kernels (rn/executor.py), and a graph with any
-other Custom op_type fails at bind with an error that names it. forward / backward of a CustomOp are never called.
+a PACT_PY / GDRQ_PY / QIL_PY node lowers to the runtime's own PACT / GDRQ / QIL kernels (rn/executor.py), and a
+graph with any other Custom op_type fails at bind with an error that names it. forward / backward of a CustomOp are
+never called. "QIL_PY" has no contrib twin, so its input list is registered here (QilProp, below): rn.graphs and a
+saved symbol's JSON build QIL nodes without the reference's core/operator/QIL.py; importing that file registers its
+own prop over this one, with the same lists.
 """
 
 _REGISTRY = {}
@@ -62,3 +65,22 @@ def register(reg_name):
 
 def get_registry():
     return dict(_REGISTRY)
+
+
+@register("QIL_PY")
+class QilProp(CustomOpProp):
+    """core/operator/QIL.py:154-176: data and three trainable (1,) inputs -- the pruning point, the clipping point
+    and gamma (fix_gamma: never read)."""
+
+    def __init__(self, is_weight="False", fix_gamma="True", nbits="4"):
+        self.is_weight = str(is_weight) == "True"
+        self.fix_gamma = str(fix_gamma) == "True"
+        self.nbits = int(nbits)
+        super().__init__(True)
+
+    def list_arguments(self):
+        return ["data", "pruning_point", "clipping_point", "gamma"]
+
+    def infer_shape(self, in_shape):
+        shape = in_shape[0]
+        return [shape, [1], [1], [1]], [shape], []

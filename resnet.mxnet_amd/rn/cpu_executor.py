@@ -6,9 +6,9 @@ gpu_list=[] meaning no GPU). A Module bound to mx.cpu() contexts runs here: ever
 (rn/executor.py) as a torch-CPU fp32 operator (oneDNN, the analogue of MXNet's MKL-DNN CPU path),
 with MXNet's semantics -- BatchNorm batch statistics with biased variance and momentum moving stats,
 fix_gamma / use_global_stats, SoftmaxOutput's p - onehot gradient, Quantization_int8 with EMA
-thresholds and the clipped STE, PACT with its learned threshold, GDRQ with its mean-based threshold,
-MXNet momentum SGD with wd_mult 0 on
-biases / betas -- and the same
+thresholds and the clipped STE, PACT with its learned threshold, GDRQ with its mean-based threshold, QIL with its
+learned pruning and clipping points, MXNet momentum SGD with wd_mult 0 on
+biases / betas and the symbol's lr_mult / wd_mult -- and the same
 flat fp32 parameter / gradient / momentum / aux buffers the GPU executor has, so Module,
 kvstore (gloo all-reduce over the flat gradient), checkpoints and metrics work unchanged.
 
@@ -49,8 +49,9 @@ class CPUExecutor:
         # the last forward's discrete decisions, kept for parity tests that replay them in a higher precision (on
         # the GPU they sit in device buffers): ReLU masks by Activation name, fake-quantized weights by quantizer
         # name, PACT codes / x < gamma masks / units by gamma name, GDRQ codes / |x| <= alpha masks / alphas / units
-        # by alpha name (weights and activations)
-        self.decisions = {"relu": {}, "wq": {}, "pact": {}, "gdrq": {}}
+        # by alpha name (weights and activations), QIL codes / interval flags / |x| > c masks by pruning-point name
+        # (weights and activations)
+        self.decisions = {"relu": {}, "wq": {}, "pact": {}, "gdrq": {}, "qil": {}}
         self._out = {}
         self._head = None
         self.num_update = 0
@@ -63,6 +64,10 @@ class CPUExecutor:
             names = [getattr(op, k, None) for k in ("weight", "bias", "gamma", "beta")]
             if op.kind == "stem" and op.bn:
                 names += [op.bn["gamma"], op.bn["beta"]]
+            if (op.qweight or {}).get("family") == "qil":
+                names += [op.qweight["prune"], op.qweight["clip"], op.qweight["gamma"]]
+            if op.kind == "qil":
+                names += [op.prune, op.clip, op.qgamma]
             for nm in names:
                 if nm and nm not in seen:
                     order.append(nm)
@@ -89,6 +94,22 @@ class CPUExecutor:
             if n.endswith("_weight") or n.endswith("_gamma"):
                 o = self.param_off[n]
                 self.wd_mult[o:o + int(np.prod(self.param_shape[n]))] = 1.0
+        self.lr_mult = None  # per element, only where some multiplier is not 1 (set_multipliers)
+        # the (pruning point, clipping point) pairs every forward clamps in place
+        self._qil_points = [(op.prune, op.clip) for op in plan.ops if op.kind == "qil"] + \
+            [(op.qweight["prune"], op.qweight["clip"]) for op in plan.ops
+             if (op.qweight or {}).get("family") == "qil"]
+
+    def set_multipliers(self, lr_mult, wd_mult):
+        """MXNet's Optimizer.lr_mult / wd_mult ({parameter name: factor}; a name without an entry: 1)."""
+        self.lr_mult = None
+        lrm = torch.ones_like(self.master)
+        for n in self.param_order:
+            o, k = self.param_off[n], int(np.prod(self.param_shape[n]))
+            self.wd_mult[o:o + k] = float(wd_mult.get(n, 1.0))
+            lrm[o:o + k] = float(lr_mult.get(n, 1.0))
+        if bool((lrm != 1.0).any()):
+            self.lr_mult = lrm
 
     def _param(self, master, name, shape=None):
         o = self.param_off[name]
@@ -109,6 +130,10 @@ class CPUExecutor:
             self._label = lab.detach().reshape(-1).to(torch.float32).clone()
 
     def forward(self, is_train=True):
+        with torch.no_grad():  # QIL's in-place clamp of its parameters (core/operator/QIL.py:51-54)
+            for pn, cn in self._qil_points:
+                self._param(self.master, pn).clamp_(min=0.0)
+                self._param(self.master, cn).clamp_(max=1.0)
         with torch.enable_grad() if is_train else torch.no_grad():
             self._master_leaf = self.master.detach().requires_grad_(is_train)
             self._run(self._master_leaf, is_train)
@@ -138,7 +163,10 @@ class CPUExecutor:
             if clip is not None and clip > 0:
                 g = g.clamp(-clip, clip)
             g = g + wd * self.wd_mult * self.master
-            self.mom.mul_(momentum).sub_(lr * g)
+            if self.lr_mult is not None:  # (lr_eff = lr * lr_mult, one fp32 product, as rn_sgd_mom_update_lrm)
+                self.mom.mul_(momentum).sub_(torch.tensor(lr, dtype=torch.float32) * self.lr_mult * g)
+            else:
+                self.mom.mul_(momentum).sub_(lr * g)
             self.master.add_(self.mom)
         self.num_update += 1
 
@@ -216,6 +244,8 @@ class CPUExecutor:
             elif k == "gdrq":
                 env[id(op.y)] = self._gdrq(get(op.x), op.alpha, op.nbits, op.fix_alpha, op.ktimes, op.lamda, False,
                                            train)
+            elif k == "qil":
+                env[id(op.y)] = self._qil(op.prune, get(op.x), P(op.prune), P(op.clip), op.nbits)
             elif k == "add":
                 y = get(op.a) + get(op.b)
                 env[id(op.y)] = F.relu(y) if op.relu else y
@@ -338,10 +368,41 @@ class CPUExecutor:
         xm = x if is_weight else x * mask.to(x.dtype)
         return v + (xm - xm.detach())  # (exactly v; the gradient is the mask's)
 
+    def _qil(self, name, x, p, c, nbits):
+        """QIL (core/operator/QIL.py:72-85, the "ste" branch; p and c were clamped when the forward began), in fp32
+        with the kernels' operation order: center, distance, alpha = 0.5 / distance, beta = (-0.5 center) / distance
+        + 0.5; t = s [|x| > c] + s (alpha |x| + beta) [p <= |x| <= c]; out = round_half_away(t L) / L. Autograd sees
+        t only (the rounding is outside the reference's recorded region): dx = dy alpha over the interval except at
+        x = 0, and the gradients of p and c through alpha and beta. The last forward's codes, interval flags and
+        |x| > c masks stay in self.decisions["qil"][name] (name: the pruning point's)."""
+        levels = float(2 ** nbits - 1)
+        center = 0.5 * (c + p)
+        distance = 0.5 * (c - p)
+        alpha = 0.5 / distance
+        beta = (-0.5 * center) / distance + 0.5
+        a = x.abs()
+        s = torch.sign(x)
+        with torch.no_grad():
+            flag = (a >= p) & (a <= c)
+            above = a > c
+        t = s * above.to(x.dtype) + s * (alpha * a + beta) * flag.to(x.dtype)
+        with torch.no_grad():
+            r = t.detach() * levels
+            tr = torch.trunc(r)  # (r - tr is exact: roundf, without floor(|r| + 0.5)'s double rounding)
+            q = tr + torch.sign(r) * ((r - tr).abs() >= 0.5).to(r.dtype)
+            v = q / levels
+            self.decisions["qil"][name] = {"codes": q, "flag": flag, "above": above, "p": float(p), "c": float(c)}
+        return v + (t - t.detach())  # (exactly v; the gradient is the transform's)
+
     def _weight(self, w, qw, train):
         """Quantization_int8 on a weight (per tensor, no clip, plain STE: symbol/quant_ops.py:17-31)."""
         if qw is None:
             return w
+        if qw.get("family") == "qil":
+            v = self._qil(qw["prune"], w, self._param(self._master_leaf, qw["prune"]),
+                          self._param(self._master_leaf, qw["clip"]), qw["nbits"])
+            self.decisions["wq"][qw["name"]] = v.detach()
+            return v
         if qw.get("family") == "gdrq":
             v = self._gdrq(w, qw["alpha"], qw["nbits"], qw["fix_alpha"], qw["ktimes"], 0.0, True, train)
             self.decisions["wq"][qw["name"]] = v.detach()

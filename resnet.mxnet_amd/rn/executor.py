@@ -189,6 +189,13 @@ class Executor:
                     if nm not in seen:
                         order.append(nm)
                         seen.add(nm)
+            # a QIL quantizer's pruning point, clipping point and (never read) gamma: the op's own, or its weight's
+            qil = op.qweight if (op.qweight or {}).get("family") == "qil" else None
+            for nm in ([qil["prune"], qil["clip"], qil["gamma"]] if qil else []) + \
+                    ([op.prune, op.clip, op.qgamma] if op.kind == "qil" else []):
+                if nm not in seen:
+                    order.append(nm)
+                    seen.add(nm)
         missing = [n for n in plan.param_names if n not in seen]
         if missing:
             raise PlanError("parameters not consumed by any lowered op: %s" % missing[:5])
@@ -227,6 +234,19 @@ class Executor:
                                 dtype=np.float32)
         self.opt_wds = torch.zeros(len(order), dtype=torch.float32, device=self.device)
         self._wd_value = None
+        self.lr_mult = np.ones(len(order), dtype=np.float32)
+        self.opt_lrms = None  # the device table of rn_sgd_mom_update*_lrm: only where a multiplier is not 1
+
+    def set_multipliers(self, lr_mult, wd_mult):
+        """MXNet's Optimizer.lr_mult / wd_mult ({parameter name: factor}; a name without an entry: 1). The
+        learning-rate table reaches the update (rn_sgd_mom_update*_lrm) only where some factor differs from 1: every
+        other graph keeps today's calls."""
+        self.wd_mult = np.array([wd_mult.get(n, 1.0) for n in self.param_order], dtype=np.float32)
+        self._wd_value = None
+        self.lr_mult = np.array([lr_mult.get(n, 1.0) for n in self.param_order], dtype=np.float32)
+        self.opt_lrms = None
+        if (self.lr_mult != 1.0).any():
+            self.opt_lrms = self.torch.from_numpy(self.lr_mult.copy()).to(self.device)
 
     def pview(self, name):
         o = self.param_off[name]
@@ -292,8 +312,10 @@ class Executor:
             if self._side_stream is not None:
                 self._spv2.value = self._side_stream.cuda_stream if self.side_enabled else self._spv.value
 
+    # (rn_weight_qil_bwd: it rewrites the weight gradient its weight-gradient call just left, on the same stream)
     WGRAD_CALLS = ("rn_conv_bwd_filter", "rn_conv_bwd_filter_ws", "rn_conv_bwd_filter_x", "rn_conv_bwd_filter_i8",
-                   "rn_stem_conv_wgrad_p4", "rn_stem_clip_wgrad", "rn_stem_clip_wgrad_chunk", "rn_stem_clip_dbeta")
+                   "rn_stem_conv_wgrad_p4", "rn_stem_clip_wgrad", "rn_stem_clip_wgrad_chunk", "rn_stem_clip_dbeta",
+                   "rn_weight_qil_bwd")
     # side-stream calls that depend on the forward only, not on the backward so far: no fork of their own
     # (they run while the side stream waits for the next dy), except the first of a step
     SIDE_PRE_CALLS = ("rn_stem_clip_mask",)
@@ -383,6 +405,7 @@ class Executor:
         self._wq_ops = []
         self._wg_ops = []  # the ops with a GDRQ weight: one rn_weight_gdrq_pack for all of them
         self._gdrq_ws = None  # rn_gdrq_fwd's block partials: one buffer for every updating GDRQ (compute stream)
+        self._wl_ops = []  # the ops with a QIL weight: one rn_weight_qil_pack for all of them
         self.fused_packs = {}  # param -> rn_wpack fields: copies rewritten by the SGD kernel itself
         self.unfused_packs = []  # packs that still run after every update (grouped, fake-quantized)
         # the grouped layers' repacks in one rn_conv_weight_pack_multi (RN_GPACK_BATCH=0: one call each)
@@ -575,9 +598,9 @@ class Executor:
         assert (d.p, d.q) == (y.h, y.w), (op.name, d.p, d.q, y.h, y.w)
         op.desc = d
         op.wc = self._zeros(self.lib.rn_conv_pack_numel(L.C.byref(d), 1), self.tdtype)
-        wgdrq = op in self._wg_ops
+        wgdrq = op in self._wg_ops or op in self._wl_ops
         if wgdrq and op.groups == 1 and not op.int8:
-            # (both compute copies written by rn_weight_gdrq_pack; their padding stays zero)
+            # (both compute copies written by rn_weight_gdrq_pack / rn_weight_qil_pack; their padding stays zero)
             op.wk = self._zeros(self.lib.rn_conv_pack_numel(L.C.byref(d), 0), self.tdtype)
         elif op.int8:
             # forward copy: the int8 codes (KRSC); the data-gradient copy stays the
@@ -716,6 +739,19 @@ class Executor:
                                   self._p(op.codes), self._p(op.unit),
                                   self._p(self._gdrq_ws) if upd else None, self._spv))
 
+    def _fwd_qil(self, op, F, I):
+        """The same in training and inference; the pruning and clipping points are read, clamped and written back on
+        the device in the flat master buffer. The values are always written; with emit_codes also the signed int8
+        codes and the unit 1 / L the consumers' int8 forward reads."""
+        op.unit = self._zeros(1, self.torch.float32)
+        op.codes = self.torch.zeros(op.x.numel, dtype=self.torch.int8, device=self.device) \
+            if op.emit_codes else None
+        c = self._call("rn_qil_fwd", self.dtype, op.x.numel, self._p(self.act(op.x)), self._pp(op.prune),
+                       self._pp(op.clip), op.nbits, self._p(self.act(op.y)), self._p(op.codes), self._p(op.unit),
+                       self._spv)
+        F.append(c)
+        I.append(c)
+
     def _fwd_add(self, op, F, I):
         if op.bn_a is not None:  # the BatchNorms of the post-activation unit tail applied inside the add
             bna, bnb = op.bn_a, op.bn_b
@@ -754,7 +790,7 @@ class Executor:
         op.desc = d
         op.wk = self._zeros(op.nh * x.cp, self.tdtype)
         op.wc = self._zeros(x.cp * _pad8(op.nh), self.tdtype)
-        if op not in self._wg_ops:  # (a GDRQ weight: both copies written by rn_weight_gdrq_pack)
+        if op not in self._wg_ops and op not in self._wl_ops:  # (a GDRQ / QIL weight: copies written by its pack)
             self._add_pack(op, d, op.wk, op.wc)
         bias = self._pp(op.bias) if op.bias else None
         c = self._call("rn_conv_fwd", L.C.byref(d), self._p(self.act(x)), self._p(op.wk),
@@ -822,6 +858,30 @@ class Executor:
             self._wg_ws = self._zeros(int(self.lib.rn_weight_gdrq_ws_bytes(len(items))) // 4, self.torch.float32)
             c_ = self._call("rn_weight_gdrq_pack", self._p(self._wg_items), len(items), self.dtype,
                             self._p(self._wg_ws), sp)
+            self.packs.insert(0, c_)
+            self.unfused_packs.insert(0, c_)
+        if self._wl_ops:
+            # every QIL weight in one rn_weight_qil_pack, ahead of the packs that read its fake-quantized copies
+            items = []
+            for op in self._wl_ops:
+                k, creal, rs = self._wquant_shape(op)
+                i8 = op.int8
+                dense = op.kind == "fc" or (op.kind == "conv" and op.groups == 1)
+                d = op.desc if dense else None
+                assert not dense or (d.k == k and d.c_real == creal and d.r * d.s == rs), op.name
+                q = op.qweight
+                items.append(L.WQilItem(
+                    master=self._pp(op.weight).value, qw=op.qw.data_ptr(),
+                    unit=op.wunit.data_ptr() if i8 else None, p=self._pp(q["prune"]).value,
+                    c=self._pp(q["clip"]).value, w_codes=op.wk8.data_ptr() if i8 else None,
+                    w_krsc=op.wk.data_ptr() if dense and not i8 else None, w_crsk=op.wc.data_ptr() if dense else None,
+                    k=k, rs=rs, c_real=creal, c_stride=d.c if dense else creal, k_pad=d.k_pad if dense else k,
+                    nbits=int(q["nbits"])))
+            arr = (L.WQilItem * len(items))(*items)
+            self._wl_items = self.torch.frombuffer(bytearray(arr), dtype=self.torch.uint8).to(self.device)
+            self._wl_ws = self._zeros(int(self.lib.rn_weight_qil_ws_bytes(len(items))) // 4, self.torch.float32)
+            c_ = self._call("rn_weight_qil_pack", self._p(self._wl_items), len(items), self.dtype,
+                            self._p(self._wl_ws), sp)
             self.packs.insert(0, c_)
             self.unfused_packs.insert(0, c_)
         if self._gpacks:
@@ -945,6 +1005,11 @@ class Executor:
             # STE): always through the batched rn_weight_gdrq_pack, built after the forward
             self._wg_ops.append(op)
             return self._p(op.qw)
+        if q.get("family") == "qil":
+            # a QIL weight (core/operator/QIL.py): always through the batched rn_weight_qil_pack, built after the
+            # forward; its backward rewrites the weight gradient (_wqil_bwd)
+            self._wl_ops.append(op)
+            return self._p(op.qw)
         if self._wq_batch:
             # one batched rn_weight_quant_pack for every weight quantizer (built after the forward):
             # the fake-quantized copy, and for the int8 convs their codes and data-gradient copy too
@@ -1039,6 +1104,8 @@ class Executor:
         self.param_done_at = {}  # param -> index in self._bwd after which its grad is final
         self._gw = {}  # id(tensor) -> last writer of its gradient buffer: ("dgrad", call index, conv op)
         self._pact_ws = None  # rn_pact_bwd's block partials: one buffer for every PACT (compute stream, plan order)
+        self._qil_ws = None  # rn_qil_bwd's, likewise
+        self._wqil_ws = None  # rn_weight_qil_bwd's: the weight gradients' stream, plan order
         self._bind_quant_folds()
         self._read_bn_bwd_modes()
         self._size_wgrad_ws()  # (before every binder: they pass the slab, or test for it)
@@ -1145,9 +1212,27 @@ class Executor:
             op.desc.dy2 = self._p(pend[1]).value
         return pend[0]
 
+    def _wqil_bwd(self, op):
+        """The backward of a QIL weight quantizer, right after the weight gradient of op (KRSC, as the master) and on
+        its stream: dw *= alpha * [p <= |w| <= c] * [w != 0] in place, and the gradients of its pruning and clipping
+        points; gamma's stays the zero the backward starts from. Before the gradient's bucket is final."""
+        q = op.qweight
+        if not q or q.get("family") != "qil":
+            return
+        if self._wqil_ws is None:  # (one buffer, made by the first weight that needs it)
+            nmax = max(int(np.prod(self.plan.param_shape(o.weight))) for o in self._wl_ops)
+            self._wqil_ws = self._zeros(int(self.lib.rn_qil_bwd_ws_bytes(nmax)) // 4, self.torch.float32)
+        n = int(np.prod(self.plan.param_shape(op.weight)))
+        self._bwd.append(self._call("rn_weight_qil_bwd", n, self._pp(op.weight), self._gp(op.weight),
+                                    self._pp(q["prune"]), self._pp(q["clip"]), self._gp(q["prune"]),
+                                    self._gp(q["clip"]), self._p(self._wqil_ws), self._spv))
+        for nm in (q["prune"], q["clip"], q["gamma"]):
+            self.param_done_at[nm] = len(self._bwd)
+
     def _bwd_fc(self, op, dy, gs):
         x = op.x
         self._bwd.append(self._wgrad_call(op.desc, self._p(self.act(x)), self._p(dy), self._gp(op.weight)))
+        self._wqil_bwd(op)
         if op.bias:
             self._bwd.append(self._call("rn_col_sum", self.dtype, x.n, op.nh, _pad8(op.nh), self._p(dy),
                                         self._gp(op.bias), 0, self._spv))
@@ -1171,6 +1256,7 @@ class Executor:
                                         self._p(dy), self._gp(op.weight), *self._wgrad_ws_args(), sp))
         else:
             self._bwd.append(self._wgrad_call(op.desc, self._p(self.act(x)), self._p(dy), self._gp(op.weight)))
+        self._wqil_bwd(op)
         self.param_done_at[op.weight] = len(self._bwd)
         if x.needs_grad:
             out, add = gs.contribute(x)
@@ -1227,6 +1313,7 @@ class Executor:
                                         self._gp(op.weight), self._p(op.clip_ext), *self._wgrad_ws_args(), sp))
         else:
             self._bwd.append(self._wgrad_call(op.dfull, self._p(op.x8), self._p(dy), self._gp(op.weight)))
+        self._wqil_bwd(op)
         self.param_done_at[op.weight] = len(self._bwd)
         if op.bn:
             self._bwd.append(self._call("rn_stem_shift_grad", L.C.byref(op.dfull), self._p(dy),
@@ -1387,6 +1474,25 @@ class Executor:
             self._gw[id(op.x)] = ("other",)
             self._bwd.append(self._call("rn_gdrq_bwd", self.dtype, op.x.numel, self._p(self.act(op.x)),
                                         self._p(dy), self._ap(op.alpha), self._p(out), self._p(add), self._spv))
+
+    def _bwd_qil(self, op, dy, gs):
+        """dx = dy * alpha over p <= |x| <= c, x != 0, and the gradients of the pruning and clipping points in one
+        pass (+ the ordered sums of its block partials, which write them); gamma's stays zero. As for PACT this
+        call is the last writer of x's gradient and fuses no BatchNorm reduction."""
+        if self._qil_ws is None:  # (one buffer, made by the first op that needs it)
+            nmax = max(o.x.numel for o in self.plan.ops if o.kind == "qil")
+            self._qil_ws = self._zeros(int(self.lib.rn_qil_bwd_ws_bytes(nmax)) // 4, self.torch.float32)
+        if op.x.needs_grad:
+            out, add = gs.contribute(op.x)
+            self._gw[id(op.x)] = ("other",)
+        else:  # (no consumer of dx: a scratch buffer takes it)
+            out, add = self._zeros(op.x.numel, self.tdtype), None
+            self._grads[("qil_dx", id(op))] = out
+        self._bwd.append(self._call("rn_qil_bwd", self.dtype, op.x.numel, self._p(self.act(op.x)), self._p(dy),
+                                    self._pp(op.prune), self._pp(op.clip), self._p(out), self._p(add),
+                                    self._gp(op.prune), self._gp(op.clip), self._p(self._qil_ws), self._spv))
+        for nm in (op.prune, op.clip, op.qgamma):
+            self.param_done_at[nm] = len(self._bwd)
 
     def _bwd_relu(self, op, dy, gs):
         if op.x.needs_grad:
@@ -1560,6 +1666,9 @@ class Executor:
         if self._wd_value != wd:
             self.opt_wds.copy_(self.torch.from_numpy(self.wd_mult * np.float32(wd)))
             self._wd_value = wd
+        if self.opt_lrms is not None:  # (some lr_mult differs from 1: the entry points with the multiplier table)
+            self._sgd_update_lrm(lr, momentum, rescale_grad, clip)
+            return
         if self.opt_packs is not None:
             L.check(self.lib.rn_sgd_mom_update_pack(len(self.param_order), self._p(self.opt_offsets),
                                                     self._p(self.opt_numels), self._p(self.opt_wds),
@@ -1575,6 +1684,23 @@ class Executor:
                                            self._p(self.grad), self._p(self.mom), None, F32, float(lr), None,
                                            float(momentum), float(rescale_grad), float(clip), self._sp()),
                 "rn_sgd_mom_update")
+        self.repack_weights()
+
+    def _sgd_update_lrm(self, lr, momentum, rescale_grad, clip):
+        n, lrm = len(self.param_order), self._p(self.opt_lrms)
+        if self.opt_packs is not None:
+            L.check(self.lib.rn_sgd_mom_update_pack_lrm(n, self._p(self.opt_offsets), self._p(self.opt_numels),
+                                                        self._p(self.opt_wds), lrm, self._p(self.master),
+                                                        self._p(self.grad), self._p(self.mom), self._p(self.opt_packs),
+                                                        self._p(self.opt_work), self.opt_nwork, self.dtype, float(lr),
+                                                        None, float(momentum), float(rescale_grad), float(clip),
+                                                        self._sp()), "rn_sgd_mom_update_pack_lrm")
+            self._run(self.unfused_packs)
+            return
+        L.check(self.lib.rn_sgd_mom_update_lrm(n, self._p(self.opt_offsets), self._p(self.opt_numels),
+                                               self._p(self.opt_wds), lrm, self._p(self.master), self._p(self.grad),
+                                               self._p(self.mom), None, F32, float(lr), None, float(momentum),
+                                               float(rescale_grad), float(clip), self._sp()), "rn_sgd_mom_update_lrm")
         self.repack_weights()
 
     # ------------------------------------------------------------------ param I/O (MXNet layouts)

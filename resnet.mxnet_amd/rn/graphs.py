@@ -173,20 +173,38 @@ def _gdrq(name, data, bits, is_weight, setting):
     return mx.sym.contrib.GDRQ(data=data, alpha=alpha, name=name, is_weight=is_weight, **_nbits(bits), **kw)
 
 
+def _qil(name, data, bits, is_weight, qil_init):
+    """create_quant_node's QIL branch (core/graph_optimize.py:169-175): the pruning point '<name>_pruning_point'
+    (starting at 0) and the clipping point '<name>_clipping_point' (at `qil_init`), trainable parameters of shape
+    (1,) with lr_mult 0.01 and wd_mult 0, and '<name>_gamma' (1.0; fix_gamma: never read), feeding
+    mx.sym.Custom(op_type="QIL_PY")."""
+    pruning = mx.sym.var(name=name + "_pruning_point", init='["constant", {"value": 0}]', lr_mult=0.01, wd_mult=0)
+    clipping = mx.sym.var(name=name + "_clipping_point", init='["constant", {"value": %s}]' % qil_init,
+                          lr_mult=0.01, wd_mult=0)
+    gamma = mx.sym.var(name=name + "_gamma", init=mx.init.Constant(1.0))
+    attrs = {"nbits": str(4 if bits is None else bits), "is_weight": str(bool(is_weight)), "fix_gamma": "True"}
+    return mx.sym.Custom(name=name, data=data, pruning_point=pruning, clipping_point=clipping, gamma=gamma, **attrs,
+                         op_type="QIL_PY")
+
+
 def quant_conv(name, data, num_filter, kernel, stride, pad=(0, 0), no_bias=True, num_group=1, in_channels=None,
                quant_mode="minmax", delay_quant=0, ema_decay=0.99, workspace=512, act_op="Quantization_int8",
                wbits=None, abits=None, pact_init=8.0, weight_op="Quantization_int8", gdrq_weight=None,
-               gdrq_act=None):
+               gdrq_act=None, qil_init=1.0):
     """int8_api.py:120-150 quant_conv_cxx: Quantization_int8 on the weight ('<name>_weight') and on
     the data ('<name>_data') feeding a plain Convolution. act_op="PACT": the data quantizer is
     mx.sym.contrib.PACT with `abits` bits instead. act_op / weight_op "GDRQ": mx.sym.contrib.GDRQ with `abits` /
-    `wbits` bits and the attributes of `gdrq_act` / `gdrq_weight` over GDRQ_ACT / GDRQ_WEIGHT."""
-    assert act_op in ("Quantization_int8", "PACT", "GDRQ"), act_op
-    assert weight_op in ("Quantization_int8", "GDRQ"), weight_op
+    `wbits` bits and the attributes of `gdrq_act` / `gdrq_weight` over GDRQ_ACT / GDRQ_WEIGHT. act_op / weight_op
+    "QIL": mx.sym.Custom(op_type="QIL_PY") with `abits` / `wbits` bits (default 4), clipping points starting at
+    `qil_init`."""
+    assert act_op in ("Quantization_int8", "PACT", "GDRQ", "QIL"), act_op
+    assert weight_op in ("Quantization_int8", "GDRQ", "QIL"), weight_op
     weight = mx.sym.Variable(name=name + "_weight", shape=(num_filter, in_channels // num_group) + tuple(kernel),
                              dtype="float32")
     if weight_op == "GDRQ":
         weight_q = _gdrq(name + "_weight", weight, wbits, True, gdrq_weight)
+    elif weight_op == "QIL":
+        weight_q = _qil(name + "_weight", weight, wbits, True, qil_init)
     else:
         weight_q = mx.sym.contrib.Quantization_int8(data=weight, name=name + "_weight", quant_mode=quant_mode,
                                                     is_weight=True, is_weight_perchannel=False, ema_decay=ema_decay,
@@ -196,6 +214,8 @@ def quant_conv(name, data, num_filter, kernel, stride, pad=(0, 0), no_bias=True,
         data_q = _pact(name + "_data", data, abits, pact_init)
     elif act_op == "GDRQ":
         data_q = _gdrq(name + "_data", data, abits, False, gdrq_act)
+    elif act_op == "QIL":
+        data_q = _qil(name + "_data", data, abits, False, qil_init)
     else:
         data_q = mx.sym.contrib.Quantization_int8(data=data, name=name + "_data", quant_mode=quant_mode,
                                                   is_weight=False, is_weight_perchannel=False, ema_decay=ema_decay,
@@ -210,13 +230,15 @@ def quant_conv(name, data, num_filter, kernel, stride, pad=(0, 0), no_bias=True,
 
 def quant_fc(name, data, num_hidden, in_channels, quant_mode="minmax", delay_quant=0, ema_decay=0.99,
              workspace=512, act_op="Quantization_int8", wbits=None, abits=None, pact_init=8.0,
-             weight_op="Quantization_int8", gdrq_weight=None, gdrq_act=None):
-    """int8_api.py:152-171 quant_fc_cxx (act_op="PACT" / "GDRQ", weight_op="GDRQ": as quant_conv)."""
-    assert act_op in ("Quantization_int8", "PACT", "GDRQ"), act_op
-    assert weight_op in ("Quantization_int8", "GDRQ"), weight_op
+             weight_op="Quantization_int8", gdrq_weight=None, gdrq_act=None, qil_init=1.0):
+    """int8_api.py:152-171 quant_fc_cxx (act_op="PACT" / "GDRQ" / "QIL", weight_op="GDRQ" / "QIL": as quant_conv)."""
+    assert act_op in ("Quantization_int8", "PACT", "GDRQ", "QIL"), act_op
+    assert weight_op in ("Quantization_int8", "GDRQ", "QIL"), weight_op
     weight = mx.sym.Variable(name=name + "_weight", shape=(num_hidden, in_channels), dtype="float32")
     if weight_op == "GDRQ":
         fc_q = _gdrq(name + "_weight", weight, wbits, True, gdrq_weight)
+    elif weight_op == "QIL":
+        fc_q = _qil(name + "_weight", weight, wbits, True, qil_init)
     else:
         fc_q = mx.sym.contrib.Quantization_int8(data=weight, name=name + "_weight", is_weight=True,
                                                 ema_decay=ema_decay, delay_quant=delay_quant, quant_mode=quant_mode,
@@ -226,6 +248,8 @@ def quant_fc(name, data, num_hidden, in_channels, quant_mode="minmax", delay_qua
         data_q = _pact(name + "_data", data, abits, pact_init)
     elif act_op == "GDRQ":
         data_q = _gdrq(name + "_data", data, abits, False, gdrq_act)
+    elif act_op == "QIL":
+        data_q = _qil(name + "_data", data, abits, False, qil_init)
     else:
         data_q = mx.sym.contrib.Quantization_int8(data=data, name=name + "_data", is_weight=False,
                                                   ema_decay=ema_decay, delay_quant=delay_quant, quant_mode=quant_mode,
@@ -254,20 +278,25 @@ def _int8_unit(x, cin, nf, stride, dim_match, name, bottle_neck, mom, qkw):
 def resnet_int8(units, num_stage, filter_list, num_classes, data_type="float32", bottle_neck=True, bn_mom=0.9,
                 workspace=512, memonger=False, grad_scale=1.0, dataset_type="imagenet", quant_mode="minmax",
                 delay_quant=0, ema_decay=0.99, act_op="Quantization_int8", wbits=None, abits=None, pact_init=8.0,
-                weight_op="Quantization_int8", gdrq_weight=None, gdrq_act=None):
+                weight_op="Quantization_int8", gdrq_weight=None, gdrq_act=None, qil_init=1.0):
     """symbol/resnet_int8.py:69-131 (the C5 config graph; BN stays separate). act_op="PACT": every
     activation quantizer that reads a ReLU output -- all but conv0's, which stays Quantization_int8 on the
     normalised image -- is mx.sym.contrib.PACT with `abits` bits; the weights stay Quantization_int8 (`wbits`).
     act_op="GDRQ": those quantizers are mx.sym.contrib.GDRQ; weight_op="GDRQ": so is every weight quantizer but
-    conv0's, which stays Quantization_int8 at its default 8 bits beside its data quantizer."""
+    conv0's, which stays Quantization_int8 at its default 8 bits beside its data quantizer. act_op / weight_op
+    "QIL": likewise with mx.sym.Custom(op_type="QIL_PY"), clipping points starting at `qil_init`."""
     assert len(units) == num_stage
     qkw0 = dict(quant_mode=quant_mode, delay_quant=delay_quant, ema_decay=ema_decay, workspace=workspace)
     qkw = dict(qkw0)
-    if weight_op != "Quantization_int8":
+    if weight_op == "QIL":
+        qkw.update(weight_op=weight_op, wbits=wbits, qil_init=qil_init)
+    elif weight_op != "Quantization_int8":
         qkw.update(weight_op=weight_op, wbits=wbits, gdrq_weight=gdrq_weight)
     elif wbits is not None:
         qkw0["wbits"] = qkw["wbits"] = wbits
-    if act_op == "GDRQ":
+    if act_op == "QIL":
+        qkw.update(act_op=act_op, abits=abits, qil_init=qil_init)
+    elif act_op == "GDRQ":
         qkw.update(act_op=act_op, abits=abits, gdrq_act=gdrq_act)
     elif act_op != "Quantization_int8":
         qkw.update(act_op=act_op, abits=abits, pact_init=pact_init)
@@ -357,6 +386,13 @@ def resnet50_gdrq(num_classes=1000, wbits=4, abits=4):
     threshold follows 3 * mean|w| (alpha starting at 0.5), 4-bit activations clipped at a fixed alpha of 1.0."""
     return resnet_int8([3, 4, 6, 3], 4, [64, 256, 512, 1024, 2048], num_classes, "float32", True, act_op="GDRQ",
                        weight_op="GDRQ", wbits=wbits, abits=abits)
+
+
+def resnet50_qil(num_classes=1000, wbits=4, abits=4):
+    """ResNet-50 with QIL quantizers (core/operator/QIL.py): 4-bit weights and activations, pruning points starting
+    at 0 and clipping points at 1.0, both learned at lr_mult 0.01; conv0 stays Quantization_int8."""
+    return resnet_int8([3, 4, 6, 3], 4, [64, 256, 512, 1024, 2048], num_classes, "float32", True, act_op="QIL",
+                       weight_op="QIL", wbits=wbits, abits=abits, qil_init=1.0)
 
 
 def resnet50(num_classes=1000):

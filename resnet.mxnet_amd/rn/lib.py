@@ -51,6 +51,12 @@ class WGdrqItem(C.Structure):
                 ("nbits", _i32), ("fix_alpha", _i32), ("ktimes", _f32)]
 
 
+class WQilItem(C.Structure):
+    _fields_ = [("master", _P), ("qw", _P), ("unit", _P), ("p", _P), ("c", _P), ("w_codes", _P), ("w_krsc", _P),
+                ("w_crsk", _P), ("k", _i32), ("rs", _i32), ("c_real", _i32), ("c_stride", _i32), ("k_pad", _i32),
+                ("nbits", _i32)]
+
+
 class PoolDesc(C.Structure):
     _fields_ = [(n, _i32) for n in ("dtype", "n", "h", "w", "c", "r", "s", "stride_h", "stride_w", "pad_h", "pad_w",
                                    "type", "global_pool", "p", "q")]
@@ -129,6 +135,9 @@ SIGNATURES = {
     "rn_sgd_mom_update": (_i32, [_i32, _P, _P, _P, _P, _P, _P, _P, _i32, _f32, _P, _f32, _f32, _f32, _P]),
     "rn_sgd_mom_update_pack": (_i32, [_i32, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _i32, _f32, _P, _f32, _f32, _f32,
                                       _P]),
+    "rn_sgd_mom_update_lrm": (_i32, [_i32, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _f32, _P, _f32, _f32, _f32, _P]),
+    "rn_sgd_mom_update_pack_lrm": (_i32, [_i32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _i32, _f32, _P, _f32, _f32,
+                                          _f32, _P]),
     "rn_sgd_pack_work": (_i32, [_i32, _P, _P, _P, _i32]),
     "rn_nchw_to_nhwc": (_i32, [_i32, _i32, _i32, _i32, _i32, _P, _P, _i32, _P]),
     "rn_cast": (_i32, [_i64, _P, _i32, _P, _i32, _P]),
@@ -150,6 +159,12 @@ SIGNATURES = {
     "rn_gdrq_bwd": (_i32, [_i32, _i64, _P, _P, _P, _P, _P, _P]),
     "rn_weight_gdrq_ws_bytes": (_i64, [_i32]),
     "rn_weight_gdrq_pack": (_i32, [_P, _i32, _i32, _P, _P]),
+    "rn_qil_fwd": (_i32, [_i32, _i64, _P, _P, _P, _i32, _P, _P, _P, _P]),
+    "rn_qil_bwd_ws_bytes": (_i64, [_i64]),
+    "rn_qil_bwd": (_i32, [_i32, _i64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rn_weight_qil_ws_bytes": (_i64, [_i32]),
+    "rn_weight_qil_pack": (_i32, [_P, _i32, _i32, _P, _P]),
+    "rn_weight_qil_bwd": (_i32, [_i64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rn_set_tuning": (_i32, [_i32, _i32]),
     "rn_last_error": (C.c_char_p, []),
     "rn_version": (_i32, []),

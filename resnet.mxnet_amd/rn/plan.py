@@ -31,6 +31,23 @@ class PlanError(RuntimeError):
     pass
 
 
+def multipliers(symbol, param_names):
+    """(lr_mult, wd_mult) as MXNet's Optimizer.set_lr_mult / set_wd_mult fill them from a symbol ({parameter name:
+    factor}; a name without an entry: 1): lr_mult from the variables' __lr_mult__; wd_mult 0 for every name that
+    ends in neither _weight nor _gamma, then the variables' __wd_mult__ over that."""
+    attrs = symbol.attr_dict()
+    lr_mult, wd_mult = {}, {}
+    for n in param_names:
+        if not (n.endswith("_weight") or n.endswith("_gamma")):
+            wd_mult[n] = 0.0
+        a = attrs.get(n, {})
+        if "__lr_mult__" in a:
+            lr_mult[n] = float(a["__lr_mult__"])
+        if "__wd_mult__" in a:
+            wd_mult[n] = float(a["__wd_mult__"])
+    return lr_mult, wd_mult
+
+
 # ============================================================================= plan (CPU)
 class TensorSpec:
     """An activation tensor: logical NCHW (or (N,F)) shape -> NHWC buffer with padded C."""
@@ -78,8 +95,8 @@ class PlanOp:
     part_src = None      # Executor._mark_bn_stats: the conv / stem whose epilogue writes this BatchNorm's statistics
     part = None          # Executor._conv_fwd_call / _fwd_stem: the buffer of those statistics' block partials
     part_mm = None       # Executor._conv_fwd_call: per-block extremes of an int8 conv's output (want_mm)
-    codes = None         # Executor._fwd_quant / _fwd_pact / _fwd_gdrq: the int8 codes a quantizer emits
-    unit = None          # Executor._fwd_quant / _fwd_pact / _fwd_gdrq: the codes' unit (one fp32 value)
+    codes = None         # Executor._fwd_quant / _fwd_pact / _fwd_gdrq / _fwd_qil: the int8 codes a quantizer emits
+    unit = None          # Executor._fwd_quant / _fwd_pact / _fwd_gdrq / _fwd_qil: the codes' unit (one fp32 value)
     pre_part = None      # Executor._bwd_add: a BatchNorm's backward reduction done by the add's ReLU backward
 
     def __init__(self, kind, name, **kw):
@@ -113,6 +130,8 @@ class Plan:
         self.qweight = {}  # id(weight Quantization_int8 node) -> quant info
         self.qweight_gdrq = {}  # id(weight GDRQ node) -> quant info (family "gdrq")
         self._gdrq_alphas = {}  # alpha variable -> the GDRQ node that owns it
+        self.qweight_qil = {}  # id(weight QIL node) -> quant info (family "qil")
+        self._qil_vars = {}  # pruning / clipping / gamma variable -> the QIL node that owns it
         self._lower()
 
     # --- shapes of every node output
@@ -211,6 +230,8 @@ class Plan:
                 self._lower_quant(n, cons)
             elif self._is_gdrq(n):
                 self._lower_gdrq(n)
+            elif self._is_qil(n):
+                self._lower_qil(n)
             elif op == "_contrib_PACT" or op == "Custom":
                 self._lower_pact(n)
             elif op == "Activation":
@@ -403,6 +424,53 @@ class Plan:
         self.ops.append(PlanOp("gdrq", n.name, x=x, y=y, alpha=av.name, nbits=nbits, fix_alpha=q["fix_alpha"],
                                ktimes=q["ktimes"], lamda=q["lamda"]))
 
+    @staticmethod
+    def _is_qil(node):
+        return node is not None and node.op == "Custom" and _parse(node.attrs.get("op_type")) == "QIL_PY"
+
+    def _lower_qil(self, n):
+        """QIL (core/graph_optimize.py:169-175): mx.sym.Custom(op_type="QIL_PY"), quantization-interval learning
+        (core/operator/QIL.py:34-176, the "ste" branch): |x| below the pruning point p goes to 0, above the clipping
+        point c to +-1, the interval between them linearly onto [0, 1], then the grid of 2^nbits - 1 steps -- the
+        output lives in [-1, 1], for weights and activations alike. p, c and gamma are ordinary trainable parameters
+        of shape (1,) in the flat parameter / gradient / momentum buffers; every forward clamps p to >= 0 and c to
+        <= 1 in place. gamma is never read (fix_gamma must be True) and its gradient is zero. A weight quantizer
+        becomes a record on its convolution (self.qweight_qil; its backward scales the weight gradient and yields
+        dp / dc: rn_weight_qil_bwd), an activation quantizer a "qil" op. The Python forward / backward of the
+        CustomOp are never run."""
+        a = n.attrs
+        if not bool(_parse(a.get("fix_gamma", True))):
+            raise PlanError("%s: QIL fix_gamma=False (a learned gamma) is not supported" % n.name)
+        nbits = int(_parse(a.get("nbits", 4)))
+        if not 1 <= nbits <= 16:
+            raise PlanError("%s: QIL nbits %d not supported" % (n.name, nbits))
+        if len(n.inputs) != 4:
+            raise PlanError("%s: QIL takes data, pruning_point, clipping_point and gamma" % n.name)
+        names = []
+        for (v, _), what in zip(n.inputs[1:], ("pruning_point", "clipping_point", "gamma")):
+            if v.op != "null" or v.name in self.input_shapes or v.name in self.aux_names:
+                raise PlanError("%s: QIL's %s must be a parameter Variable" % (n.name, what))
+            if v.name in self._qil_vars or v.name in names:
+                raise PlanError("%s: %s %s is shared with QIL node %s (not supported)"
+                                % (n.name, what, v.name, self._qil_vars.get(v.name, n.name)))
+            names.append(v.name)
+        for nm in names:
+            self._qil_vars[nm] = n.name
+        q = dict(family="qil", name=n.name, prune=names[0], clip=names[1], gamma=names[2], nbits=nbits,
+                 is_weight=bool(_parse(a.get("is_weight", False))))
+        src = n.inputs[0][0]
+        if q["is_weight"]:
+            if src.op != "null":
+                raise PlanError("%s: weight quantization of a computed tensor" % n.name)
+            q["param"] = src.name
+            self.qweight_qil[id(n)] = q
+            return
+        x = self.tensor(src) if id(src) in self.tensors or id(src) in self.alias else None
+        if x is None or x.kind != "act":
+            raise PlanError("%s: QIL of a non-activation tensor" % n.name)
+        y = self._new_tensor(n, x.shape)
+        self.ops.append(PlanOp("qil", n.name, x=x, y=y, prune=names[0], clip=names[1], qgamma=names[2], nbits=nbits))
+
     def _nonneg(self, t):
         """Is activation tensor `t` known to be >= 0: written by a BatchNorm with fused ReLU, a relu op, an add
         with ReLU, or a pooling of one of those (PACT has no lower clip: only then are its codes 0 .. 2^nbits - 1)?"""
@@ -422,27 +490,27 @@ class Plan:
         non-negative (_nonneg); otherwise its convolution multiplies the fake-quantized values. A GDRQ quantizer's
         codes are signed, -L .. L with L = 2^nbits - 1: it qualifies with nbits <= 7 on the data side whatever its
         input's sign, and on the weight side (Quantization_int8 weights: nbits <= 8); mixed pairs qualify side by
-        side."""
-        producer = {id(op.y): op for op in self.ops if op.kind in ("quant", "pact", "gdrq")}
+        side. A QIL quantizer's codes are signed too, -L .. L with unit 1 / L: the same rule on both sides."""
+        producer = {id(op.y): op for op in self.ops if op.kind in ("quant", "pact", "gdrq", "qil")}
         on = os.environ.get("RN_INT8_MFMA", "1") != "0"
         for op in self.ops:
-            if op.kind in ("quant", "pact", "gdrq"):
+            if op.kind in ("quant", "pact", "gdrq", "qil"):
                 op.emit_codes = False
-            if op.kind in ("pact", "gdrq"):
-                op.codes_wgrad = False  # (never for PACT / GDRQ: the values are always written)
+            if op.kind in ("pact", "gdrq", "qil"):
+                op.codes_wgrad = False  # (never for PACT / GDRQ / QIL: the values are always written)
         for op in self.ops:
             if op.kind != "conv":
                 continue
             q = producer.get(id(op.x))
             if q is not None and q.kind == "pact":
                 q_ok = q.nbits <= 7 and self._nonneg(q.x)
-            elif q is not None and q.kind == "gdrq":
+            elif q is not None and q.kind in ("gdrq", "qil"):
                 q_ok = q.nbits <= 7  # (signed codes -L .. L, L = 2^nbits - 1 <= 127; the input's sign is free)
             else:
                 q_ok = q is not None and q.q["nbits"] <= 8
-            # (a GDRQ weight's codes reach 2^nbits - 1, a Quantization_int8 weight's 2^(nbits - 1) - 1)
+            # (a GDRQ / QIL weight's codes reach 2^nbits - 1, a Quantization_int8 weight's 2^(nbits - 1) - 1)
             w_ok = op.qweight is not None and \
-                op.qweight["nbits"] <= (7 if op.qweight.get("family") == "gdrq" else 8)
+                op.qweight["nbits"] <= (7 if op.qweight.get("family") in ("gdrq", "qil") else 8)
             op.int8 = bool(on and w_ok and q_ok and op.groups == 1 and op.x.cp % 16 == 0 and
                            op.xf is None)
             op.qsrc = q if op.int8 else None
@@ -533,13 +601,17 @@ class Plan:
             return self.qweight[id(p)]["param"]
         if id(p) in self.qweight_gdrq:
             return self.qweight_gdrq[id(p)]["param"]
+        if id(p) in self.qweight_qil:
+            return self.qweight_qil[id(p)]["param"]
         if p.op != "null":
             raise PlanError("%s: computed weights are not supported" % node.name)
         return p.name
 
     def _weight_quant(self, node, idx=1):
         p = node.inputs[idx][0]
-        return self.qweight.get(id(p)) if self._is_quant(p) else self.qweight_gdrq.get(id(p))
+        if self._is_quant(p):
+            return self.qweight.get(id(p))
+        return self.qweight_gdrq.get(id(p)) or self.qweight_qil.get(id(p))
 
     def _conv_attrs(self, n):
         k = _tup(n.attrs["kernel"])

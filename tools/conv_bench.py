@@ -1,7 +1,7 @@
 """Per-shape timing of the conv kernels (fwd / dgrad / wgrad) over the unique convolutions of a
 graph (default ResNet-50 v2, batch 256, bf16) -- the inner loop for conv-kernel work.
 
-python tools/conv_bench.py [--graph resnet50|resnext50|resnet50_int8|resnet50_pact|resnet50_gdrq|mobilenet] [--iters 20] [--only fwd,dgrad,wgrad]
+python tools/conv_bench.py [--graph resnet50|resnext50|resnet50_int8|resnet50_pact|resnet50_gdrq|resnet50_qil|mobilenet] [--iters 20] [--only fwd,dgrad,wgrad]
 Prints one line per unique shape (count = occurrences per step) and the per-step totals.
 python tools/conv_bench.py --only dgbn,bnst,bnrc --cold --filter conv1: the BatchNorm backward chain behind each conv1
 data gradient, stored against recomputed (in the step these tensors are not cache-resident: time them cold).
@@ -35,7 +35,7 @@ def main():
     from rn.plan import Plan, _pad8
     sym = {"resnet50": graphs.resnet50, "resnext50": graphs.resnext50_32x4d,
            "resnet50_int8": graphs.resnet50_int8, "resnet50_pact": graphs.resnet50_pact,
-           "resnet50_gdrq": graphs.resnet50_gdrq,
+           "resnet50_gdrq": graphs.resnet50_gdrq, "resnet50_qil": graphs.resnet50_qil,
            "mobilenet": graphs.mobilenet_1_0}[a.graph]()
     plan = Plan(sym, [("data", (a.batch, 3, 224, 224))], [("softmax_label", (a.batch,))])
     lib = L.load()

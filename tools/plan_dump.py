@@ -1,7 +1,7 @@
 """Print the executor's bound call plan for a graph, built without a GPU (Executor(plan, "cpu")), as text that
 does not depend on addresses: two trees bind the same plan exactly when their dumps are byte-identical. CPU-only.
 usage: python tools/plan_dump.py GRAPH [--shape N,C,H,W] [--dtype bfloat16|float32]
-GRAPH: a builder in rn.graphs (resnet50, resnext50_32x4d, resnet50_int8, ...; default shape 2,3,64,64) or one of the
+GRAPH: a builder in rn.graphs (resnet50, resnext50_32x4d, resnet50_int8, resnet50_qil, ...; default shape 2,3,64,64) or one of the
 16-class graphs of tests/test_stream_hazards_cpu.py (small_resnet20, small_resnet50, small_resnext50,
 small_resnet_int8; their shapes there).
 
@@ -95,7 +95,7 @@ class Dump:
             for i, (name, _, args) in enumerate(getattr(ex, lname)):
                 side = " side" if lname == "_bwd" and i in ex._side_idx else ""
                 yield "%s %d%s %s(%s)" % (lname, i, side, name, ", ".join(self.fmt(a) for a in args))
-        for tname in ("_wq_items", "_wg_items", "opt_packs", "opt_work"):
+        for tname in ("_wq_items", "_wg_items", "_wl_items", "opt_packs", "opt_work"):
             t = getattr(ex, tname, None)
             if t is not None:
                 words = t.contiguous().view(-1).view(ex.torch.uint8).numpy().view("<u8")
@@ -105,6 +105,17 @@ class Dump:
         for k in sorted(ex.param_done_at):
             yield "param_done_at %s %d" % (k, ex.param_done_at[k])
         yield "buckets %s" % (ex.buckets(),)
+        # the update's multiplier tables as Module.init_optimizer sets them; printed only where the symbol moves
+        # one (a graph without __lr_mult__ / __wd_mult__ attributes dumps as it always did)
+        from rn.plan import multipliers
+        lr_mult, wd_mult = multipliers(ex.plan.symbol, ex.plan.param_names)
+        name_rule = {n: 0.0 for n in ex.plan.param_names if not (n.endswith("_weight") or n.endswith("_gamma"))}
+        if lr_mult or wd_mult != name_rule:
+            ex.set_multipliers(lr_mult, wd_mult)
+            yield "update %s" % ("rn_sgd_mom_update_pack_lrm" if ex.opt_packs is not None else "rn_sgd_mom_update_lrm")
+            for n, lm, wm in zip(ex.param_order, ex.lr_mult, ex.wd_mult):
+                if lm != 1.0 or wm != (0.0 if n in name_rule else 1.0):
+                    yield "multipliers %s lr %r wd %r" % (n, float(lm), float(wm))
 
 
 def main():
